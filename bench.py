@@ -34,13 +34,17 @@ Workloads (--config, BASELINE.json configs; synthetic SURVEY 8d ticks):
                H=32, ~15 training days = 3600 ticks + 720 validation ticks),
                phi 1e-4 on 510300 ticks; 7 with the adversary (USE_ARL).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints one JSON line.  The CPU baseline (rank 0, N=1 only) runs BEFORE
-the GPU is touched: the reference-equivalent batch-1 torch loop
-(oracle/ref_loop.py) under fork Pools of 16 and 8 workers on a bounded sample
-of the same workload, plus the C oracle as a "best CPU" line.
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K
+generations, writes the last generation's results with --dump-outputs and
+prints the headline figures.  --full adds the rest of the line: the CPU
+baseline (rank 0, N=1 only), which runs BEFORE the GPU is touched -- the
+reference-equivalent batch-1 torch loop (oracle/ref_loop.py) under fork Pools
+of 16 and 8 workers on a bounded sample of the same workload, plus the C oracle
+as a "best CPU" line -- and, after the timed window, the per-kernel durations
+and the policy kernel's roofline (a second, eager run of the same generations).
 """
 from __future__ import annotations
 
@@ -84,14 +88,20 @@ def parse():
     ap.add_argument("--hidden", type=int, default=0, help="override: TradingPolicy hidden width")
     ap.add_argument("--ticks", type=int, default=0, help="override: training ticks")
     ap.add_argument("--val-ticks", type=int, default=-1, help="override: validation ticks")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline (before the GPU is touched) and, after the timed window, "
+                         "the per-kernel profile and roofline; the line then carries cpu_baseline, kernels, "
+                         "roofline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed generation computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--profile-steps", type=int, default=0,
-                    help="timed-window generations re-run eagerly and timed kernel by kernel with HIP events "
+                    help="--full: timed-window generations re-run eagerly and timed kernel by kernel with HIP events "
                          "(0: all of them)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-episodes", type=int, default=256,
-                    help="episodes in the CPU-baseline sample (256 x 4560 ticks: ~20 core-seconds on Pool(16))")
-    ap.add_argument("--pmc", default="", help="PMC traffic summary JSON (default: newest for this config)")
+                    help="--full: episodes in the CPU-baseline sample (256 x 4560 ticks: ~20 core-seconds on Pool(16))")
+    ap.add_argument("--pmc", default="", help="--full: PMC traffic summary JSON (default: newest for this config)")
     ap.add_argument("--shard-of", type=int, default=1,
                     help="strong-scaled configs (4, 5): run ONE rank's shard of an N-GPU run on this GPU "
                          "(ceil(P/N) individuals per population; no exchange) and label the line '1 of N ranks'")
@@ -283,7 +293,7 @@ def main():
         print(f"warning: --gpus {args.gpus} but WORLD_SIZE={world}", file=sys.stderr)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(spec, args.cpu_episodes)  # before the GPU is initialised (fork Pool)
 
     import torch
@@ -339,6 +349,98 @@ def main():
     res = sess.finish()
     ms_per_step = dt / args.steps * 1e3
     value = K * P_glob * T * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sess)
+
+    n_rank = shard_capacity(P_glob, world)
+    best_val = bool(sess.best_val)
+    kernels = gen_kernel_us = roofline = dominant = None
+    if args.full:
+        kernels, gen_kernel_us, roofline, dominant = kernel_profile(
+            args, sgmm, spec, (tr, va, st), tmp, n_rank, best_val, shard_of)
+
+    if rank == 0:
+        gens_per_s = args.steps / dt
+        if cpu:
+            # the other half of BASELINE's metric: generations per second of the same
+            # workload on the CPU path = its env-steps/s / the workload's training
+            # env-steps per generation (every population, the reference's Pool loop)
+            steps_per_gen = K * P_glob * T
+            cpu["generations_per_s"] = cpu["value"] / steps_per_gen
+            cpu["env_steps_per_generation"] = steps_per_gen
+            cpu["gpu_generations_per_s"] = gens_per_s
+            cpu["generations_speedup"] = gens_per_s / cpu["generations_per_s"]
+        out = {
+            # a shard line is ONE rank's share of a strong-scaled run: its own metric
+            # name and config id, so it cannot be taken for the whole config
+            "metric": METRIC if shard_of == 1 else f"{METRIC} [one rank's shard: 1 of {shard_of}]",
+            "value": value, "unit": "env-steps/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "higher_is_better": True, "scaling": spec["scaling"], "vs_baseline": None,
+            "dtype": "f32+f64", "data": "synthetic",
+            "config": {"workload": describe(spec, world, P_glob, best_val) + (
+                           f"; ONE RANK'S SHARD: 1 of {shard_of} ranks (ceil(P/{shard_of}) = {P} individuals per "
+                           f"population, rollout + tell on this GPU, no exchange)" if shard_of > 1 else ""),
+                       "config_id": args.config if shard_of == 1 else f"{args.config}/shard-1-of-{shard_of}",
+                       "shard_of": shard_of,
+                       "populations": K, "population_global": P_glob, "population_per_gpu": n_rank,
+                       "phis": [p for p, _, _ in spec["pops"]], "hidden": H, "ticks_train": T, "ticks_val": Tv,
+                       "adversary": spec["arl"], "val_mode": "best" if best_val else "fused",
+                       "parallelism": f"population shards x{world}" + (" + RCCL all-gather" if world > 1 else ""),
+                       "hip_graph": bool(sess.use_graph),
+                       "graph_has_exchange": bool(sess.full_graph) if world > 1 else None,
+                       "graph_capture_error": getattr(sess, "capture_error", None),
+                       "plan_overrides": plan or None,
+                       "walk_feedback": not args.no_walk_feedback},
+            "generations_per_s": gens_per_s,
+            "final_train_f": [float(h["train_f"][-1]) for _, h in res],
+        }
+        if args.full:
+            out |= {"roofline": roofline,
+                    "cpu_baseline": cpu,
+                    "speedup_vs_cpu_baseline": (value / cpu["value"]) if cpu else None,
+                    "kernels": kernels,
+                    "dominant_kernel": dominant,
+                    "gen_kernel_time_us": gen_kernel_us}
+        print(json.dumps(out))
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, sess):
+    """What the last timed generation left with the session's caller, one
+    DIR/<name>.npy each (float64; the masters float32): every individual's
+    training fitness and trade count (per population, then its fused validation
+    results when val_mode is fused), the validation of the new masters (best
+    validation), the last history row of each population (train_f, val_f,
+    sigma_after, train_trades, val_trades, best_idx, flags) and the masters the
+    generation's tell produced.  A few hundred kB at the BASELINE configs."""
+    import numpy as np
+    from sgmm_amd.drl_engine import HIST_DTYPE
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    f, t = sess.rec.both
+    arrays = {"fitness": f.cpu().numpy().astype(np.float64),
+              "trades": t.cpu().numpy().astype(np.float64),
+              "masters": sess.masters.cpu().numpy().astype(np.float32),
+              "best_masters": sess.best_masters.cpu().numpy().astype(np.float32)}
+    if sess.masters_adv is not None:
+        arrays["masters_adv"] = sess.masters_adv.cpu().numpy().astype(np.float32)
+    if sess.vout is not None:
+        arrays["val_fitness"] = sess.vout[0].cpu().numpy().astype(np.float64)
+        arrays["val_trades"] = sess.vout[1].cpu().numpy().astype(np.float64)
+    rows = sess.hist[:, sess.generations - 1].cpu().numpy().reshape(sess.K, -1).view(HIST_DTYPE).reshape(sess.K)
+    arrays["history_last"] = np.stack([rows[n].astype(np.float64) for n in HIST_DTYPE.names], axis=1)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a))
+
+
+def kernel_profile(args, sgmm, spec, data, tmp, n_rank, best_val, shard_of):
+    """--full: (kernels, gen_kernel_time_us, roofline, dominant_kernel) of the timed window."""
+    import torch
+    from sgmm_amd import _lib
+    tr, va, st = data
+    K, H, T, Tv = len(spec["pops"]), spec["H"], spec["T"], spec["Tv"]
 
     # per-kernel durations over the TIMED window: the same generations re-run
     # eagerly on this rank's shard with the timed run's seeds (so the identical
@@ -347,7 +449,6 @@ def main():
     # replays launch the identical kernels.  The policy kernel gets cheaper as
     # the populations train, so its first / last / mean over the window are
     # reported and the mean is the roofline's launch time.
-    n_rank = shard_capacity(P_glob, world)
     g0 = args.warmup
     n_prof = args.steps if args.profile_steps <= 0 else min(args.steps, max(args.profile_steps, 1))
     peng = make_engine(sgmm, spec, n_rank, tmp, False, False, args.val_mode,  # the timed run's seeds
@@ -375,7 +476,6 @@ def main():
 
     # roofline of the policy kernel (the FP32 compute kernel of the path): the
     # frontier kernel from 768 episodes per launch (the measured crossover), the table below that
-    best_val = bool(sess.best_val)
     # the training launch: training episodes (+ every validation episode when fused)
     steps_per_launch = K * n_rank * (T if best_val else T + Tv)
     fl = flop_per_step(H)
@@ -419,51 +519,7 @@ def main():
                                "frac": gbps / HBM_PEAK_GBPS, "source": pmc.get("file")}
     dominant = max(kernels.items(), key=lambda kv: kv[1]["avg_us"] * kv[1]["launches"])[0] if kernels else None
 
-    if rank == 0:
-        gens_per_s = args.steps / dt
-        if cpu:
-            # the other half of BASELINE's metric: generations per second of the same
-            # workload on the CPU path = its env-steps/s / the workload's training
-            # env-steps per generation (every population, the reference's Pool loop)
-            steps_per_gen = K * P_glob * T
-            cpu["generations_per_s"] = cpu["value"] / steps_per_gen
-            cpu["env_steps_per_generation"] = steps_per_gen
-            cpu["gpu_generations_per_s"] = gens_per_s
-            cpu["generations_speedup"] = gens_per_s / cpu["generations_per_s"]
-        out = {
-            # a shard line is ONE rank's share of a strong-scaled run: its own metric
-            # name and config id, so it cannot be taken for the whole config
-            "metric": METRIC if shard_of == 1 else f"{METRIC} [one rank's shard: 1 of {shard_of}]",
-            "value": value, "unit": "env-steps/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": spec["scaling"], "vs_baseline": None,
-            "dtype": "f32+f64", "data": "synthetic",
-            "config": {"workload": describe(spec, world, P_glob, best_val) + (
-                           f"; ONE RANK'S SHARD: 1 of {shard_of} ranks (ceil(P/{shard_of}) = {P} individuals per "
-                           f"population, rollout + tell on this GPU, no exchange)" if shard_of > 1 else ""),
-                       "config_id": args.config if shard_of == 1 else f"{args.config}/shard-1-of-{shard_of}",
-                       "shard_of": shard_of,
-                       "populations": K, "population_global": P_glob, "population_per_gpu": n_rank,
-                       "phis": [p for p, _, _ in spec["pops"]], "hidden": H, "ticks_train": T, "ticks_val": Tv,
-                       "adversary": spec["arl"], "val_mode": "best" if best_val else "fused",
-                       "parallelism": f"population shards x{world}" + (" + RCCL all-gather" if world > 1 else ""),
-                       "hip_graph": bool(sess.use_graph),
-                       "graph_has_exchange": bool(sess.full_graph) if world > 1 else None,
-                       "graph_capture_error": getattr(sess, "capture_error", None),
-                       "plan_overrides": plan or None,
-                       "walk_feedback": not args.no_walk_feedback},
-            "generations_per_s": gens_per_s,
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "speedup_vs_cpu_baseline": (value / cpu["value"]) if cpu else None,
-            "kernels": kernels,
-            "dominant_kernel": dominant,
-            "gen_kernel_time_us": gen_kernel_us,
-            "final_train_f": [float(h["train_f"][-1]) for _, h in res],
-        }
-        print(json.dumps(out))
-    if world > 1:
-        dist.destroy_process_group()
+    return kernels, gen_kernel_us, roofline, dominant
 
 
 if __name__ == "__main__":

@@ -2,7 +2,7 @@
 # no trace domains combined with --pmc).  Output under gpurun_out/pmc_*.
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-B="python bench.py --steps 30 --warmup 2 --no-cpu-baseline --profile-steps 2"
+B="python bench.py --steps 30 --warmup 2 --full --no-cpu-baseline --profile-steps 2"
 i=0
 for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU" \
            "FETCH_SIZE" "WRITE_SIZE" \
