@@ -68,11 +68,28 @@ void plan_init() {
     }
 #endif
 }
-}  // namespace
-
 int32_t plan_value(int k) {
     std::call_once(g_plan_once, plan_init);
     return (k >= 0 && k < SGMM_PLAN_N) ? g_plan[k].load(std::memory_order_relaxed) : -1;
+}
+}  // namespace
+
+PlanKnobs plan_knobs() {
+    PlanKnobs k;
+    k.policy_path = plan_value(SGMM_PLAN_POLICY_PATH);
+    k.groups = plan_value(SGMM_PLAN_GROUPS);
+    k.lane_split = plan_value(SGMM_PLAN_LANE_SPLIT);
+    k.tail = plan_value(SGMM_PLAN_TAIL);
+    k.four = plan_value(SGMM_PLAN_FOUR);
+    k.min_eps = plan_value(SGMM_PLAN_MIN_EPS);
+    k.table_sp = plan_value(SGMM_PLAN_TABLE_SP);
+    k.scan_threads = plan_value(SGMM_PLAN_SCAN_THREADS);
+    k.reorder_weights = plan_value(SGMM_PLAN_REORDER_WEIGHTS);
+    k.spill = plan_value(SGMM_PLAN_SPILL);
+    k.seq_sum = plan_value(SGMM_PLAN_SEQ_SUM);
+    k.fused_scan = plan_value(SGMM_PLAN_FUSED_SCAN);
+    k.lanes_scan = plan_value(SGMM_PLAN_LANES_SCAN);
+    return k;
 }
 
 void set_error(const char* fmt, ...) {

@@ -14,10 +14,9 @@
 #include <stdint.h>
 
 #include "../../include/sgmm.h"
+#include "sgmm_plan.h"  // kWave
 
 namespace sgmm {
-
-constexpr int kWave = 64;
 
 // ReLU as one v_med3_f32(a, 0, +inf) on the float pipe.  +inf goes through an
 // empty asm (opaque to the optimizer, hoisted once per kernel): a visible

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../../include/sgmm.h"
+#include "sgmm_plan.h"
 
 namespace sgmm {
 
@@ -70,8 +71,9 @@ struct ProfScope {
 
 inline bool supported_hidden(int h) { return h == 8 || h == 16 || h == 32 || h == 64; }
 
-// Launch-plan override of knob k (SGMM_PLAN_*), or -1 for the default rule
+// Snapshot of the launch-plan overrides (SGMM_PLAN_*, -1 = the default rule):
+// taken once per C-ABI entry, so every launch of the call follows one plan
 // (sgmm_plan_set; the -DSGMM_EXPERIMENTS build seeds them from SGMM_* variables)
-int32_t plan_value(int k);
+PlanKnobs plan_knobs();
 
 }  // namespace sgmm

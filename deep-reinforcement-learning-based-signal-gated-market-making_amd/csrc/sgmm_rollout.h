@@ -6,13 +6,11 @@
 #include "sgmm_device.h"
 #include "sgmm_ga_device.h"
 #include "sgmm_internal.h"
+#include "sgmm_plan.h"  // the constants the launch-plan rules share with the kernels
 
 namespace sgmm {
 
-constexpr int kChunk = 64;          // ticks per chunk in the path scan
 constexpr int kSeg = 4096;          // ticks summed per LDS segment
-constexpr int kScanBlock = 256;
-constexpr int kMaxLen = 1 << 17;    // max ticks per episode of the no-adversary table path (its scan's LDS chunk tables)
 
 struct EpArrays {
     const int32_t* genome;
@@ -25,13 +23,13 @@ struct EpArrays {
     const int32_t* order;  // frontier kernel: episode of order position p (NULL: p)
     // frontier kernel: the episodes at order positions [0, whole) are cut into
     // g0 groups of 64 chunks (one wave each, chunks of frontier_len(T, g0)
-    // ticks), the rest into gtail groups (frontier_plan); ngrp = the larger,
+    // ticks), the rest into gtail groups (frontier_plan, sgmm_plan.h); ngrp = the larger,
     // the layout of the records (64 ngrp per episode) and plane padding; the
     // path scan reads an episode's group count from its first record
     int32_t ngrp;
     int32_t g0, gtail, whole;
     // path scans: the episode sums as the plain sequential chain (1) or by the
-    // exact parallel binade method (0) -- the same bits either way (rollout_impl's rule)
+    // exact parallel binade method (0) -- the same bits either way (LaunchPlan::seq_sum)
     int32_t seq_sum = 0;
 };
 
@@ -156,32 +154,18 @@ struct IntC {
 __device__ __forceinline__ int mbcnt64(uint64_t m) {
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
-constexpr int kFrontierLanes = 64;     // chunks per wave (one per lane)
 #ifndef SGMM_FR_PRIO_EXTRA
 #define SGMM_FR_PRIO_EXTRA 160
 #endif
 constexpr int kFrPrioExtra = SGMM_FR_PRIO_EXTRA;  // a walk's issue priority from 0.625 extra slots per tick on average
-constexpr int kFrontierMaxWaves = 16;  // waves (64-chunk groups) per episode
 // the chunk records (map, trade counts, merge info) of an episode cut into nw
 // groups: 64 nw per episode, chunk c of episode e at e * 64 nw + c
 __host__ __device__ __forceinline__ int64_t frontier_rec(int e, int nw, int c) {
     return (int64_t)e * kFrontierLanes * nw + c;
 }
-constexpr int64_t kFrontierMaxLen = (int64_t)kFrontierLanes * 65532;  // ticks: chunks (multiples of 4) below 2^16 ticks, 16-bit trade counts
 typedef __attribute__((address_space(3))) const float lds_cf;
 typedef __attribute__((address_space(3))) const f32x4 lds_cf4;
-// ticks per chunk with nw waves (64 nw chunks) per episode
-__host__ __device__ __forceinline__ int frontier_len(int T, int nw) {
-    const int c = (T + kFrontierLanes * nw - 1) / (kFrontierLanes * nw);
-    return c < 4 ? 4 : (c + 3) & ~3;  // a multiple of 4: a scan thread's 4 ticks stay in one chunk
-}
-// the episode's block of plane rows: nw groups of frontier_len(T, nw) x 64 rows
-// <= T + 256 nw rows (T rounded up to 64 nw chunks of a multiple of 4),
-// starting on a 128-byte line (16 rows), so blocks at step_off + pad e
-// (rounded up to 16, pad = 256 nw + 16) never overlap and no two episodes
-// share a line; the plane stride covers total_steps + pad n (rew_stride).
-// Group g's rows start at base + g * CL * 64 (frontier_row within the group)
-__host__ __device__ __forceinline__ int64_t frontier_pad(int nw) { return 256LL * nw + 16; }
+// the episode's block of plane rows (frontier_pad, sgmm_plan.h)
 __device__ __forceinline__ int64_t frontier_base(int64_t step_off, int e, int nw) {
     return (step_off + frontier_pad(nw) * e + 15) & ~int64_t(15);
 }
@@ -295,10 +279,11 @@ struct FusedHandoff {
     uint32_t st_tr;
     uint32_t pad;
 };
+static_assert(sizeof(FusedHandoff) == kFusedHandoffBytes, "the workspace layout's hand-off size");
 // fused path scan: a frontier walk's LDS holds a 512-tick window of the sum and
 // its group's 64 start states / merge infos; at most two groups per episode
+// (kFusedMaxGroups, sgmm_plan.h)
 constexpr int kFusedWin = 512;
-constexpr int kFusedMaxGroups = 2;
 constexpr int kSpillTicks = 64;  // a spilled chunk's remaining ticks fit one wave (lane = tick)
 
 // wave_map_scan within segments of SEG = 16, 32 or 64 lanes

@@ -11,20 +11,30 @@
 //     but the policy only sees (signal_t, inventory) and the inventory takes
 //     at most 8 values (caps +-2 -> 5), so the per-(tick, state) work can be
 //     laid out in parallel:
-//     - k_policy_frontier (many episodes, H = 16 / 32): one wave per episode,
+//     The launch plan picks one of five (PolicyKernel, sgmm_plan.h):
+//     - Frontier, k_policy_frontier (many episodes or episodes beyond kMaxLen,
+//       H = 16 / 32, no adversary; sgmm_frontier.hip): one wave per walk,
 //       lane = chunk, only the states the chunk's paths occupy are evaluated;
-//     - k_policy_table_v3 (few episodes, and the adversary path): every
-//       (tick, inventory[, adversary flags]) state, one wave per 64 ticks, the
-//       H x H layer on v_mfma_f32_16x16x4_f32 (its k-ordered fused chain IS
-//       the canonical dot-product order); k_policy_table_mfma (round 1's
-//       schedule, H = 64) and k_policy_table (VALU, H = 8) likewise.
+//     - the tables evaluate every (tick, inventory[, adversary flags]) state,
+//       the H x H layer on v_mfma_f32_16x16x4_f32 (its k-ordered fused chain
+//       IS the canonical dot-product order):
+//       TableSp, k_policy_table_sp (H = 16 / 32, no adversary, launches of at
+//       most kTableSpChunks chunks): one workgroup per chunk, one wave per state;
+//       TableV3, k_policy_table_v3 (H = 16 / 32, no adversary, larger
+//       launches): one wave per 64 ticks;
+//       TableMfma, k_policy_table_mfma (round 1's schedule): H = 64 and the
+//       adversary path at H = 16 / 32 / 64;
+//     - TableValu, k_policy_table (one lane per (tick, state) on the VALU):
+//       H = 8, and any H when forced, the tests' independent cross-check.
 //     Output: per chunk its transition byte-map and the trade count along the
 //     path from each start state, per tick the path planes (the reward along
 //     the chunk's path from each start state).  With the adversary: 2 fill
 //     bits per (inventory, previous fills) state (u64) and one float64 reward
 //     plane per state.
 //
-//  2. path scan (one workgroup, or one wave, per episode): chunk start states
+//  2. path scan (ScanKernel: Wave = k_path_scan, one workgroup or one wave per
+//     episode; Lanes = k_path_scan_lanes, 2-4 episodes per workgroup; Arl =
+//     k_path_scan_arl; Fused = inside the frontier walks): chunk start states
 //     from the chunk maps, each tick's reward = one row of its chunk's path
 //     plane, summed in the reference's sequential float64 order (bit-exact,
 //     exact_sum_window), trades from the chunk counts.  The adversary variant
@@ -717,11 +727,11 @@ __global__ __launch_bounds__(kWave * 4, H <= 16 ? (NSI <= 5 ? 5 : 4) : 2) void k
 // slots for the same episode) -- and rewrites the order so the next launch
 // walks the lightest populations whole and cuts the heaviest into halves.
 // Scheduling only: every result is per episode and independent of the order.
-// (SGMM_FRONTIER_REORDER=0 keeps the caller's order.)
+// (sgmm_populations::walk_order = NULL -- walk_feedback=False in the engine --
+// keeps the caller's order; SGMM_PLAN_REORDER_WEIGHTS sets the two weights.)
 // The job rides along as one extra workgroup of the validation table launch
 // that follows (k_policy_table_sp), which hides its ~6 us of latency; alone
 // (k_walk_reorder) where that launch takes another path.
-constexpr int kReorderMaxPops = 64;
 struct ReorderJob {
     const uint32_t* wslots;
     int32_t* order;  // null: no job
@@ -967,11 +977,7 @@ __global__ __launch_bounds__(kWave * NSI) void k_policy_table_sp(
 // and ~11 run jumps.
 constexpr int kSumBlk = 16;
 constexpr int kSumTpt = 4;          // rewards gathered per path-scan thread
-constexpr int kScanThreads = 1024;  // path-scan workgroup
 constexpr int kScanWin = kScanThreads * kSumTpt;
-constexpr int kScanAt1024 = 256;  // path-scan workgroup: 1024 threads up to this many episodes,
-constexpr int kScanAt512 = 512;   // 256 up to this many, one wave above
-constexpr int kScanArlAt1024 = 1024;  // adversary path scan: 1024 threads up to this many, kScanBlock above
 constexpr int64_t kMLo = (1LL << 52) + 1, kMHi = (1LL << 53) - 1;
 constexpr int32_t kZeroRun = INT32_MAX;  // a block's prediction: all its values are +-0.0
 constexpr int kHeadBlocks = 8;           // blocks added the reference way when a sum starts at +0.0
@@ -1707,10 +1713,6 @@ __global__ __launch_bounds__(TPB) void k_path_scan(
 // W and the window measured (profiles/r06_lanes/, scan of config 3 / of config 5's
 // 1-of-8 shard): W = 16 57.8 / 40.5 us, 8 59.5 / 33.9, 4 55.5 / 31.1, 2 53.5 / 33.5;
 // 1024-tick windows 56.5-59.6 / 33.8 (one episode per wave: 72.2 / 37.5)
-#ifndef SGMM_LANES_W
-#define SGMM_LANES_W 4
-#endif
-constexpr int kLanesW = SGMM_LANES_W;       // episodes per workgroup (lanes_w picks 2 or 4 per launch)
 #ifndef SGMM_LANES_WIN
 #define SGMM_LANES_WIN 512
 #endif
@@ -2253,14 +2255,6 @@ static int check_episodes(const sgmm_ticks* tk, const sgmm_episodes* eps, const 
     return SGMM_OK;
 }
 
-// Chunk groups per episode in the frontier kernel (one wave each).  A walk's
-// time is set by its serial chain of ticks, not by its SIMD's load, so when the
-// launch has fewer than two walks per SIMD the episodes are cut into 2-4
-// groups of 64 chunks of proportionally fewer ticks;
-// each extra group pays for tracking every start state of its chunks until
-// their paths merge.  SGMM_PLAN_GROUPS = 1..16 forces the count (records and
-// plane padding are laid out for the launch's count, frontier_rec / frontier_pad).
-constexpr int kFrontierAutoWaves = 8;  // the default rule's cap
 // SIMDs of the current device (cached per device id; 256 CUs if the query fails)
 static int simd_count() {
     constexpr int kMaxDev = 64;
@@ -2278,108 +2272,12 @@ static int simd_count() {
     }
     return n;
 }
-// The launch's chunk-group plan: g0 groups for the episodes at order positions
-// [0, whole), gtail groups for the rest; gmax = the record / padding layout.
-struct FrontierPlan {
-    int32_t g0, gtail, whole, gmax;
-    int64_t waves;  // walks (64-chunk groups)
-    int32_t ls;     // waves per walk (lane split, k_policy_frontier<H, NSI, LS>)
-};
-static FrontierPlan frontier_plan(int32_t n) {
-    FrontierPlan p{1, 1, std::max(n, 0), 1, std::max<int64_t>(n, 0), 1};
-    const int ls_force = plan_value(SGMM_PLAN_LANE_SPLIT);  // tests / experiments: waves per walk
-    if (ls_force == 2 || ls_force == 4) p.ls = ls_force;
-    {
-        const int g = plan_value(SGMM_PLAN_GROUPS);
-        if (g >= 1 && g <= kFrontierMaxWaves) {
-            p.g0 = p.gtail = p.gmax = g;
-            p.waves = (int64_t)n * g;
-            return p;
-        }
-    }
-    if (n <= 0) return p;
-    // two walks per SIMD (measured, config 5's 1-of-8 shard, 1024 episodes of
-    // 3600 ticks: 317 / 274 / 313 / 336 us at 1 / 2 / 3 / 4 groups, round 4;
-    // 270 / 272 / 331 us at 2 / 4 / 8 groups, round 5; splitting lanes instead,
-    // 283-311 us, profiles/r05_small)
-    const int64_t S = simd_count();
-    p.g0 = p.gtail = p.gmax = (int32_t)std::max<int64_t>(1, std::min<int64_t>(kFrontierAutoWaves, 2 * S / n));
-    // from half as many episodes as SIMDs down, two waves per walk (lane split):
-    // four waves per SIMD without more chunk starts (the 1-of-16 shard, 512
-    // episodes: frontier + scan 248.5 us at G = 4 with two waves per walk against
-    // 255.9 us at G = 8 and 270.6 us at G = 4 with one, profiles/r05_small/ls_*, c5s16_fr4)
-    if (n <= S / 2 && ls_force < 0) p.ls = 2;
-    // Whole walks are dispatched one per SIMD per run of S waves, so n = a S + r
-    // leaves r SIMDs with a walk more than the others, and the walks on those
-    // SIMDs end last.  The r episodes at the end of the order are cut into
-    // ~S / r groups instead: the last run of waves becomes ~S shorter walks,
-    // one per SIMD (1536 = 1024 + 512 -> 1024 whole walks and 512 episodes in 2
-    // groups; config 3's 2560 = 2 x 1024 + 512 -> 2048 + 512 in 2 groups took
-    // the policy kernel from 547 to 525 us, before the four-walk rule below).
-    // SGMM_PLAN_TAIL = 0 keeps every walk whole.
-    const bool tail = plan_value(SGMM_PLAN_TAIL) != 0;
-    const int64_t r = n % S;
-    const int fourv = plan_value(SGMM_PLAN_FOUR);
-    const bool four = fourv != 0;  // experiments: 0 = no four-walk rule, 2 = whole walks and quarters
-    if (tail && fourv == 2 && p.g0 == 1 && 4 * n - 4 * S >= 3 * (S / 2) && n < 4 * S) {
-        // experiment: four walks per SIMD as whole walks and quarters, (4n - 4S) / 3
-        // whole (config 3: 2048 whole + 512 episodes in quarters)
-        p.whole = (int32_t)((4 * n - 4 * S) / 3);
-        p.gtail = p.gmax = 4;
-    } else if (tail && four && p.g0 == 1 && 2 * n - 4 * S >= S / 2 && n < 4 * S) {
-        // from 2.5 episodes per SIMD up to 4: four walks per SIMD, 2n - 4S whole
-        // and the rest in halves, one whole and three half walks per SIMD (config
-        // 3: 2560 = 1024 whole + 1536 in halves; 660.5-668.0 against 670.3-670.6 us
-        // per generation for 2048 whole + 512 in halves, and 690-699 us for all in
-        // halves, profiles/r05_ab/ab20_*, ab21_*)
-        p.whole = (int32_t)(2 * n - 4 * S);
-        p.gtail = p.gmax = 2;
-    } else if (tail && p.g0 == 1 && n > S && r > 0) {
-        const int64_t gt = std::max<int64_t>(1, std::min<int64_t>(kFrontierMaxWaves, (S + r / 2) / r));
-        if (gt > 1) {
-            p.whole = (int32_t)(n - r);
-            p.gtail = p.gmax = (int32_t)gt;
-        }
-    }
-    p.waves = (int64_t)p.whole * p.g0 + (int64_t)(n - p.whole) * p.gtail;
-    return p;
-}
-// the record / plane-padding layout of a launch of n episodes
-static int32_t frontier_groups(int32_t n) { return frontier_plan(n).gmax; }
 
-// Spill deadline of a frontier launch (FrontierArgs::spill_budget, 10 ns units):
-// SGMM_PLAN_SPILL microseconds after a walk's start, 0 = no spill.  A walk
-// still running then stops once its chunks have <= kSpillTicks ticks left;
-// k_frontier_spill runs the rest tick-parallel.
-constexpr int kSpillDefault = 0;
-static uint32_t spill_budget(const sgmm_episodes* eps, const FrontierPlan&) {
-    int v = plan_value(SGMM_PLAN_SPILL);
-    if (v < 0) v = kSpillDefault;
-    if (v == 0 || eps->max_len <= 0) return 0;
-    return (uint32_t)std::min<int64_t>((int64_t)v * 100, 0x7FFFFFFF);
-}
-
-
-// plane stride: every tick, plus (no adversary: the frontier kernel may run)
-// the frontier layout's padding rows per episode, frontier_pad(G) with G the
-// launch's chunk groups; the adversary planes are table rows only
-static int64_t rew_stride(int64_t steps, int32_t n, bool arl) {
-    const int64_t pad = arl ? 0 : frontier_pad(frontier_groups(n)) * n;
-    return (steps + pad + 31) & ~int64_t(31);
-}
-
-static EpArrays ep_arrays(const sgmm_episodes* e, bool with_adv) {
+// rs: the plane stride of the batch's workspace layout (WorkspaceLayout::rs)
+static EpArrays ep_arrays(const sgmm_episodes* e, bool with_adv, int64_t rs) {
     return EpArrays{e->genome, with_adv ? e->adv : nullptr, e->tick_off, e->len, e->step_off,
-                    e->param, rew_stride(e->total_steps, e->n, with_adv), e->order, 1, 1, 1, e->n};
+                    e->param, rs, e->order, 1, 1, 1, e->n};
 }
-
-static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
-// Policy kernel selection, SGMM_PLAN_POLICY_PATH: default = the frontier
-// kernel for many episodes, else the f32-MFMA table; 1 / 2 force either; 3
-// forces the VALU table (one lane per (tick, state)), an independent
-// cross-check in the tests.
-static bool table_valu() { return plan_value(SGMM_PLAN_POLICY_PATH) == 3; }
 
 }  // namespace sgmm
 
@@ -2400,53 +2298,16 @@ extern "C" int sgmm_debug_tstamps(unsigned long long* host, int n_waves) {
 }
 #endif
 
-// Workspace layout (256-byte aligned sections), per batch of total_steps ticks:
-//   no adversary: u64 cmaps[nc] | u64 ctr[nc] (nc = total_steps/64 + n + 1 chunk
-//                 slots) | u32 kinfo[n * 64 G] | u32 wslots[n * 64] | u32 wspill[n * 64] | f64 path planes
-//                 rew[n_states][rs] (rs = total_steps + frontier_pad(G) n,
-//                 rounded up to 32; G = frontier_groups(n))
-//   adversary:    u64 fills[total_steps] | f64 rew[n_states][rs] (rs =
-//                 total_steps rounded up to 32)
-//   (frontier kernel: cmaps / ctr hold u64 maps / u32[8] trade counts at the
-//   records e * 64 G + c, kinfo the merge tick | p0 << 29 of each record; the
-//   sections are sized for both the table and the frontier layout)
-static size_t n_chunk_slots(int32_t n, int64_t steps) { return (size_t)steps / kChunk + (size_t)n + 1; }
-static size_t n_frontier_slots(int32_t n) { return (size_t)n * kFrontierLanes * frontier_groups(n); }  // chunk records
-static size_t ws_cmaps(int32_t n, int64_t steps) {
-    return align256(std::max(n_chunk_slots(n, steps), n_frontier_slots(n)) * sizeof(uint64_t));
-}
-static size_t ws_ctr(int32_t n, int64_t steps) {
-    return align256(std::max(n_chunk_slots(n, steps) * sizeof(uint64_t), n_frontier_slots(n) * 8 * sizeof(uint32_t)));
-}
-// u32 kinfo[n * 256]: per chunk record the merge tick | p0 << 29
-static size_t ws_kinfo(int32_t n) { return align256(n_frontier_slots(n) * sizeof(uint32_t)); }
-static size_t ws_fills(int64_t steps) { return align256((size_t)steps * sizeof(uint64_t)); }
-// u32 wslots[n * 64]: the frontier launch's MLP slots per walk, [e * G + group] (G <= 16)
-static size_t ws_wslots(int32_t n) { return align256((size_t)n * 64 * sizeof(uint32_t)); }
-// u32 wspill[n * 64]: per frontier wave (<= 16 groups x 4 waves per episode) the
-// tick offset at which it spilled, 0 if it did not
-static size_t ws_wspill(int32_t n) { return align256((size_t)n * 64 * sizeof(uint32_t)); }
-// the fused scan's per-episode arrival words and chain hand-offs (FrontierArgs::hstate, handoff)
-static size_t ws_arrive(int32_t n) {
-    return align256((size_t)n * sizeof(uint32_t)) + align256((size_t)n * sizeof(FusedHandoff));
-}
-
-// The workspace of a batch with n_inventory inventory values, with or
-// without the adversary (then 4 * n_inventory states: inventory x previous
-// fill flags).  The adversary flag is explicit: 4 * n_inventory <= 8 for one
-// or two inventory values, so a state count alone cannot tell the layouts apart.
-static size_t rollout_ws_bytes(int32_t n_episodes, int64_t total_steps, int32_t nsi, bool arl) {
-    if (total_steps < 0 || nsi <= 0 || nsi > 8 || n_episodes < 0) return 0;
-    if (arl)  // fill codes, per-state planes rew[state * rs + row]
-        return ws_fills(total_steps) + (size_t)rew_stride(total_steps, n_episodes, true) * (size_t)(4 * nsi) * sizeof(double);
-    return ws_cmaps(n_episodes, total_steps) + ws_ctr(n_episodes, total_steps) + ws_kinfo(n_episodes) +
-           ws_wslots(n_episodes) + ws_wspill(n_episodes) + ws_arrive(n_episodes) +
-           (size_t)rew_stride(total_steps, n_episodes, false) * (size_t)nsi * sizeof(double);
+// The workspace of a batch on the current device under the current knobs
+// (workspace_layout, sgmm_plan.h; rollout_impl carves the same layout)
+static size_t rollout_ws_bytes(int32_t n_episodes, int64_t total_steps, int32_t nsi, bool arl,
+                               const PlanKnobs& knobs) {
+    return workspace_layout(n_episodes, total_steps, nsi, arl, simd_count(), knobs).bytes;
 }
 
 extern "C" size_t sgmm_rollout_workspace_bytes(int32_t n_episodes, int64_t total_steps, int32_t n_inventory,
                                                int32_t with_adversary) {
-    return rollout_ws_bytes(n_episodes, total_steps, n_inventory, with_adversary != 0);
+    return rollout_ws_bytes(n_episodes, total_steps, n_inventory, with_adversary != 0, plan_knobs());
 }
 
 // ABI 3 form: n_states > 8 means the adversary layout with n_states / 4
@@ -2454,51 +2315,24 @@ extern "C" size_t sgmm_rollout_workspace_bytes(int32_t n_episodes, int64_t total
 // with fewer than 3 inventory values)
 extern "C" size_t sgmm_rollout_workspace_size(int32_t n_episodes, int64_t total_steps,
                                               int32_t n_states) {
-    if (n_states > 8) return n_states % 4 ? 0 : rollout_ws_bytes(n_episodes, total_steps, n_states / 4, true);
-    return rollout_ws_bytes(n_episodes, total_steps, n_states, false);
+    if (n_states > 8) return n_states % 4 ? 0 : rollout_ws_bytes(n_episodes, total_steps, n_states / 4, true, plan_knobs());
+    return rollout_ws_bytes(n_episodes, total_steps, n_states, false, plan_knobs());
 }
 
-// Frontier kernel or table: the frontier kernel does ~1/3 of the table's
-// matrix work but walks each episode serially (one wave per episode), so it
-// needs many episodes to fill the chip; it is also the only path for episodes
-// longer than kMaxLen.  SGMM_PLAN_POLICY_PATH forces either,
-// SGMM_PLAN_MIN_EPS moves the threshold.  Measured crossover (one rank's
-// shard of config 5, H = 32, 3600 ticks, per generation, profiles/r03_c5_shard*):
-// 256 episodes table 235 / frontier 363 us, 512: 365 / 435, 1024: 633 / 525,
-// 2048: 1078 / 572 -- the lines crossed near 700 episodes.  With 2-4 chunk
-// groups per episode (round 4, training launch alone, profiles/r04_ab/r04m_*,
-// r04n_*): 256 episodes table 167 / frontier 162 us, 512: 255-263 / 195-204.
-constexpr int kFrontierMinEps = 512;
-static bool use_frontier(bool arl, int hidden, const sgmm_episodes* eps) {
-    if (arl || (hidden != 16 && hidden != 32)) return false;
-    if (eps->max_len > kMaxLen) return true;
-    const int path = plan_value(SGMM_PLAN_POLICY_PATH);
-    if (path == 1) return true;
-    if (path > 1) return false;
-    const int m = plan_value(SGMM_PLAN_MIN_EPS);
-    return eps->n >= (m > 0 ? m : kFrontierMinEps);
-}
-
-// The one-state-per-wave table for launches of at most kTableSpChunks chunks
-// (SGMM_PLAN_TABLE_SP = 0 / 1 forces v3 / it, for A/B and the tests)
-constexpr int64_t kTableSpChunks = 256;
-static bool table_sp(int nch, int n_ep) {
-    if (const int v = plan_value(SGMM_PLAN_TABLE_SP); v >= 0) return v != 0;
-    return (int64_t)nch * n_ep <= kTableSpChunks;
-}
-
-// rj (may be null): a walk-order job to run as the state-parallel table's extra
-// workgroup; *rj_done tells whether it did
+// The MFMA tables (LaunchPlan::policy): TableSp and TableV3 for H = 16 / 32
+// without the adversary, TableMfma for H = 64 and the adversary path.
+// rj (TableSp; may be null): a walk-order job to run as the state-parallel
+// table's extra workgroup
 template <int H>
-static void launch_table_mfma(bool arl, int nsi, int max_len, int n_ep, hipStream_t s,
+static void launch_table_mfma(PolicyKernel kind, bool arl, int nsi, int max_len, int n_ep, hipStream_t s,
                               const sgmm_ticks& tk, const EpArrays& ep,
                               const sgmm_env_params* params, const GenomeSrc& src, int32_t inv_min,
                               uint64_t* ctr, uint64_t* cmaps, uint64_t* fills, double* rew,
-                              const ReorderJob* rj = nullptr, bool* rj_done = nullptr) {
+                              const ReorderJob* rj) {
     const int nch = (max_len + kChunk - 1) / kChunk;
     const dim3 grid((nch + 3) / 4, n_ep), block(kWave * 4);  // 4 chunks (waves) per block
     if constexpr (H <= 32) {
-        if (!arl && table_sp(nch, n_ep)) {
+        if (kind == PolicyKernel::TableSp) {
             const ReorderJob job = rj ? *rj : ReorderJob{nullptr, nullptr, 0, 0, 0, 1};
             const dim3 g2(nch, n_ep + (job.order ? 1 : 0)), b2(kWave * nsi);  // one workgroup per chunk, one wave per state
             if (nsi <= 5)
@@ -2507,10 +2341,9 @@ static void launch_table_mfma(bool arl, int nsi, int max_len, int n_ep, hipStrea
             else
                 SGMM_LAUNCH((k_policy_table_sp<H, 8>), g2, b2, 0, s, tk, ep, params, src, inv_min, nsi, ctr, cmaps,
                             rew, job);
-            if (rj_done) *rj_done = job.order != nullptr;
             return;
         }
-        if (!arl) {
+        if (kind == PolicyKernel::TableV3) {
             if (nsi <= 5)
                 SGMM_LAUNCH((k_policy_table_v3<H, 5>), grid, block, 0, s, tk, ep, params, src, inv_min, nsi, ctr, cmaps,
                             rew);
@@ -2560,22 +2393,6 @@ extern "C" int sgmm_ordered_sum(const double* values, int64_t n, double init, do
     return SGMM_OK;
 }
 
-// path-scan workgroup size for n episodes (256 CUs): one 16-wave workgroup per
-// CU while they fit, then 8-wave, then 4-wave workgroups
-static int scan_threads(int64_t n) {
-    {
-        const int t = plan_value(SGMM_PLAN_SCAN_THREADS);
-        if (t == 64 || t == 256 || t == 512 || t == 1024) return t;
-    }
-    // beyond 512 episodes one-wave workgroups: the exact-sum walk is serial,
-    // so many episodes resident per CU beat fewer wider workgroups (config 3:
-    // 193 -> 145 us per scan, tools/gpu_sc1.sh; config 5's 1-of-8 shard, 1024
-    // episodes: 110 -> 74 us, profiles/r04_ab/r04k_*; round 6: 54.7 against 69.3 /
-    // 94.6 us for 256 / 512 threads, profiles/r06_scanw/).  From 257 to 512
-    // episodes 4-wave workgroups (1024-tick windows): config 5's 1-of-16 shard
-    // (512 episodes) 49.8 against 61.7 us with 512 threads, 52.4 with one wave
-    return n <= kScanAt1024 ? kScanThreads : (n <= kScanAt512 ? 256 : kWave);
-}
 
 template <int NSM, bool FR>
 static void launch_path_scan(int nt, int64_t n, size_t lds, hipStream_t s, const EpArrays& ep,
@@ -2596,40 +2413,6 @@ static void launch_path_scan(int nt, int64_t n, size_t lds, hipStream_t s, const
                     rew, fitness, trades, step);
 }
 
-// Episode sums of a path scan: the plain sequential chain or the exact parallel
-// binade method (exact_sum_window); both give the reference's bits.  Measured per
-// shape, 20 generations each (profiles/r06_seq/): the sequential chain wins in the
-// one-wave and 4-wave scans of many GA-trained episodes -- config 3 89.0 -> 75.7 us,
-// config 5's 8 192 / 4 096 / 2 048 / 1 024 / 512 episodes 187.9 / 112.8 / 68.0 /
-// 55.9 / 50.7 -> 177.4 / 102.4 / 61.8 / 40.1 / 32.9 us -- and in the validation
-// scans (11.5-12.7 -> 10.3-11.4 us); the parallel method wins where one 16-wave
-// workgroup sums each long episode (config 2 15.7 vs 26.8 us, config 6 18.5 vs
-// 27.0) and in the adversary scan (config 4 39.9 vs 44.9, its 1-of-4 shard 32.5 vs
-// 41.9).  SGMM_PLAN_SEQ_SUM forces either.
-static bool scan_seq_sum(int nt, bool arl, bool validation) {
-    if (const int v = plan_value(SGMM_PLAN_SEQ_SUM); v >= 0) return v != 0;
-    if (validation) return true;
-    return !arl && nt <= 256;
-}
-
-// The path scan fused into the frontier launch (k_policy_frontier<..., FS>): each
-// walk sums its own episode (the sequential chain) while the launch's longer walks
-// still run, and the last record of a population runs the tell -- no separate
-// scan launch.  Where it applies: one wave per walk, <= kFusedMaxGroups groups, no
-// spill, no tail or the tell's argmax (mode 3), not where the parallel sum is forced.
-// The default takes it for launches of whole walks only (round 6, profiles/r06_fused/,
-// per generation: config 5 1.344-1.360 -> 1.327-1.332 ms, its 1-of-2 shard
-// 0.789-0.794 -> 0.759-0.761, 1-of-4 0.489-0.490 -> 0.469-0.471); with halves the
-// chain hand-offs and the in-kernel sums on SIMDs shared with walks cost more than
-// the separate scan (config 3 0.639-0.641 -> 0.646-0.650, the 1-of-8 shard 0.333 ->
-// 0.372 ms).  SGMM_PLAN_FUSED_SCAN forces it off (0) or on where it applies (1).
-static bool fused_scan_plan(const FrontierPlan& plan, uint32_t spill, const StepArgs& step, bool vt) {
-    const int v = plan_value(SGMM_PLAN_FUSED_SCAN);
-    if (v == 0 || vt || spill || plan.ls != 1 || plan.gmax > kFusedMaxGroups) return false;
-    if (plan_value(SGMM_PLAN_SEQ_SUM) == 0) return false;  // the parallel method forced
-    if (step.st && step.mode != 3) return false;
-    return v == 1 || plan.gmax == 1;
-}
 
 // zero n words (the fused scan's arrival counters)
 __global__ __launch_bounds__(1024) void k_zero_u32(uint32_t* __restrict__ p, int32_t n) {
@@ -2637,45 +2420,14 @@ __global__ __launch_bounds__(1024) void k_zero_u32(uint32_t* __restrict__ p, int
     if (i < n) p[i] = 0u;
 }
 
-// The frontier path scan with kLanesW episodes per workgroup and their chains in
-// the lanes of one wave (k_path_scan_lanes): where the one-wave scan would run the
-// sequential chain, with no tail or the tell's argmax (mode 3) and populations of
-// whole workgroups (config 3: scan 72 -> 55.5 us, 0.627-0.639 -> 0.605-0.612 ms
-// per generation; config 5's 1-of-8 shard 37.5 -> 31.1 us).  SGMM_PLAN_LANES_SCAN forces it off (0) or on where it applies (1).
-static bool lanes_scan(int nt, bool seq, const StepArgs& step, int32_t pop_eps) {
-    const int v = plan_value(SGMM_PLAN_LANES_SCAN);
-    if (v == 0 || !seq || (step.st && step.mode != 3)) return false;
-    if (step.st && step.pop_eps > 0 && step.pop_eps % 4 != 0) return false;
-    (void)pop_eps;
-    return v > 0 || nt == kWave;
-}
-// episodes per lanes-scan workgroup: 2 from 2 048 episodes, 4 below (config 3 / 2 560
-// episodes: scan 53.5 against 55.5 us; config 5's 1-of-8 shard / 1 024: 31.1 against
-// 33.5 us with 2, profiles/r06_lanes/); SGMM_PLAN_LANES_SCAN = 2 or 4 forces it
-static int lanes_w(int32_t n, const StepArgs& step) {
-    const int v = plan_value(SGMM_PLAN_LANES_SCAN);
-    if (v == 2 || v == 4) return v;
-    (void)step;
-    return n >= 2048 ? 2 : kLanesW;
-}
 
-// the launches the feedback applies to: a mixed whole / halves plan of one wave
-// per walk, whole populations of equal-length episodes, the caller's writable
-// walk order (sgmm_populations::walk_order)
-static bool walk_reorder(const sgmm_episodes* eps, const FrontierPlan& plan, const GenomeSrc& src,
-                         const int32_t* walk_order) {
-    const int P = src.pop_eps;
-    return walk_order && eps->order == walk_order && P > 0 && eps->n % P == 0 && eps->n / P >= 2 &&
-           eps->n / P <= kReorderMaxPops &&
-           plan.ls == 1 && plan.g0 == 1 && (plan.gtail == 2 || plan.gtail == 4) && plan.whole > 0 && plan.whole < eps->n &&
-           eps->total_steps == (int64_t)eps->n * eps->max_len;
-}
-
-// table + path scan (+ the generation tail when step.st) for one batch
+// policy kernel + path scan (+ the generation tail when step.st) for one batch:
+// resolves the launch plan once (resolve_plan, sgmm_plan.h: kernels, chunk
+// groups, workspace layout) from the entry point's knob snapshot and executes it.
 // walk_order: the caller's writable walk order (eps->order points at it) for the
 // walk-order feedback; rj_out: a training launch with the feedback hands its job
 // here instead of launching it; rj_in: a job to run inside (or before) this launch
-static int rollout_impl(const sgmm_ticks* ticks, const sgmm_episodes* eps,
+static int rollout_impl(const PlanKnobs& knobs, const sgmm_ticks* ticks, const sgmm_episodes* eps,
                         const sgmm_env_params* params, const GenomeSrc& src, bool arl,
                         int32_t hidden, double* fitness, int32_t* trades, void* workspace,
                         size_t workspace_bytes, const StepArgs& step, hipStream_t s,
@@ -2685,145 +2437,128 @@ static int rollout_impl(const sgmm_ticks* ticks, const sgmm_episodes* eps,
     if (eps->n == 0) return SGMM_OK;
     const int32_t nsi = eps->inv_max - eps->inv_min + 1;
     const int32_t ns = arl ? 4 * nsi : nsi;
-    const size_t need = rollout_ws_bytes(eps->n, eps->total_steps, nsi, arl);
-    if (!workspace || workspace_bytes < need) {
-        set_error("workspace %zu bytes < required %zu", workspace_bytes, need);
+    LaunchShape shape;
+    shape.n = eps->n;
+    shape.max_len = eps->max_len;
+    shape.total_steps = eps->total_steps;
+    shape.nsi = nsi;
+    shape.hidden = hidden;
+    shape.arl = arl;
+    shape.simds = simd_count();
+    shape.tail = step.st != nullptr;
+    shape.mode = step.mode;
+    shape.pop_eps = step.pop_eps;
+    shape.src_pop_eps = src.pop_eps;
+    shape.walk_feedback = walk_order && eps->order == walk_order;
+    const LaunchPlan plan = resolve_plan(shape, knobs);
+    const WorkspaceLayout& ws = plan.ws;
+    if (!workspace || workspace_bytes < ws.bytes) {
+        set_error("workspace %zu bytes < required %zu", workspace_bytes, ws.bytes);
         return SGMM_ERR_WORKSPACE;
     }
     char* w = reinterpret_cast<char*>(workspace);
-    uint64_t* ctr = nullptr;
-    uint64_t* cmaps = nullptr;
-    uint64_t* fills = nullptr;
-    uint32_t* kinfo = nullptr;
-    uint32_t* wslots = nullptr;
-    uint32_t* wspill = nullptr;
-    uint32_t* arrive = nullptr;
-    double* rew;
-    if (arl) {
-        fills = reinterpret_cast<uint64_t*>(w);
-        rew = reinterpret_cast<double*>(w + ws_fills(eps->total_steps));
-    } else {
-        const size_t a = ws_cmaps(eps->n, eps->total_steps), b = ws_ctr(eps->n, eps->total_steps);
-        cmaps = reinterpret_cast<uint64_t*>(w);
-        ctr = reinterpret_cast<uint64_t*>(w + a);
-        kinfo = reinterpret_cast<uint32_t*>(w + a + b);
-        wslots = reinterpret_cast<uint32_t*>(w + a + b + ws_kinfo(eps->n));
-        const size_t c = a + b + ws_kinfo(eps->n) + ws_wslots(eps->n);
-        wspill = reinterpret_cast<uint32_t*>(w + c);
-        arrive = reinterpret_cast<uint32_t*>(w + c + ws_wspill(eps->n));
-        rew = reinterpret_cast<double*>(w + c + ws_wspill(eps->n) + ws_arrive(eps->n));
-    }
-    EpArrays ep = ep_arrays(eps, arl);
-    const ReorderJob* rj_fold = nullptr;
-    bool rj_done = false;
-    const bool fr = use_frontier(arl, hidden, eps);
-    const FrontierPlan plan = frontier_plan(eps->n);
+    const auto at = [w](size_t off) -> void* { return off == kNoSection ? nullptr : w + off; };
+    uint64_t* cmaps = static_cast<uint64_t*>(at(ws.cmaps));
+    uint64_t* ctr = static_cast<uint64_t*>(at(ws.ctr));
+    uint32_t* kinfo = static_cast<uint32_t*>(at(ws.kinfo));
+    uint32_t* wslots = static_cast<uint32_t*>(at(ws.wslots));
+    uint32_t* wspill = static_cast<uint32_t*>(at(ws.wspill));
+    uint32_t* arrive = static_cast<uint32_t*>(at(ws.arrive));
+    FusedHandoff* handoff = static_cast<FusedHandoff*>(at(ws.handoff));
+    uint64_t* fills = static_cast<uint64_t*>(at(ws.fills));
+    double* rew = static_cast<double*>(at(ws.rew));
+    EpArrays ep = ep_arrays(eps, arl, ws.rs);
+    const bool fr = plan.policy == PolicyKernel::Frontier;
     if (fr) {
-        ep.ngrp = plan.gmax;
-        ep.g0 = plan.g0;
-        ep.gtail = plan.gtail;
-        ep.whole = plan.whole;
+        ep.ngrp = plan.fr.gmax;
+        ep.g0 = plan.fr.g0;
+        ep.gtail = plan.fr.gtail;
+        ep.whole = plan.fr.whole;
     }
-    const bool vt = step.st && (step.mode == 2 || step.mode == 4);  // the validation launches (profiled separately)
+    const bool vt = plan.validation;  // the validation launches are profiled separately
     SGMM_REQUIRE(fr || arl || eps->max_len <= kMaxLen,
                  "max_len=%d > %d needs the frontier kernel (hidden 16 or 32) or the adversary path", eps->max_len,
                  kMaxLen);
     SGMM_REQUIRE(!fr || eps->max_len <= kFrontierMaxLen, "max_len=%d > %lld ticks per episode",
                  eps->max_len, (long long)kFrontierMaxLen);
+    const ReorderJob* rj_fold = nullptr;
     if (rj_in && rj_in->order) {
         // a walk-order job rides along in this launch's state-parallel table when it takes
         // that path and its workspace use ends below the job's slot counts; otherwise it
         // runs first, before this launch can touch the workspace
-        const int nch = (eps->max_len + kChunk - 1) / kChunk;
-        const bool fold = !fr && !arl && eps->max_len > 0 && (hidden == 16 || hidden == 32) && !table_valu() &&
-                          table_sp(nch, eps->n) &&
-                          reinterpret_cast<const char*>(rj_in->wslots) >= w + rollout_ws_bytes(eps->n, eps->total_steps, nsi, arl);
-        if (fold) {
+        if (plan.policy == PolicyKernel::TableSp && eps->max_len > 0 &&
+            reinterpret_cast<const char*>(rj_in->wslots) >= w + ws.bytes) {
             rj_fold = rj_in;
         } else {
             SGMM_LAUNCH(k_walk_reorder, dim3(1), dim3(kScanThreads), 0, s, *rj_in);
             SGMM_LAUNCHED();
-            rj_done = true;
         }
     }
-    const uint32_t spill = fr ? spill_budget(eps, plan) : 0u;
-    const bool fused = fr && eps->max_len > 0 && fused_scan_plan(plan, spill, step, vt);
-    if (fr && eps->max_len > 0) {
+#define SGMM_TABLE_ARGS s, *ticks, ep, params, src, eps->inv_min, ctr, cmaps, fills, rew
+    if (eps->max_len <= 0) {
+        // no ticks: the scan alone writes every episode's (empty) record
+    } else if (fr) {
         FrontierArgs fa{*ticks, ep, params, src, eps->inv_min, nsi, cmaps, reinterpret_cast<uint32_t*>(ctr),
-                        kinfo, rew, wslots, wspill, spill};
-        if (fused) {
+                        kinfo, rew, wslots, wspill, plan.spill};
+        if (plan.scan == ScanKernel::Fused) {
             fa.fitness = fitness;
             fa.trades = trades;
             fa.hstate = arrive;
-            fa.handoff = reinterpret_cast<FusedHandoff*>(reinterpret_cast<char*>(arrive) + align256((size_t)eps->n * sizeof(uint32_t)));
+            fa.handoff = handoff;
             fa.n_eps = eps->n;
             fa.step = step;
             // the arrival words start at zero (the wave that ends an episode's chain
             // resets its word; a workspace is not zeroed before its first use).  A kernel,
             // not hipMemsetAsync: replayed after other launches, a captured memset
             // node left stale values here (tools/diag_fused2.py, round 6)
-            if (plan.gmax > 1)
+            if (plan.fr.gmax > 1)
                 SGMM_LAUNCH(k_zero_u32, dim3((eps->n + 1023) / 1024), dim3(1024), 0, s, arrive, eps->n);
         }
         ProfScope prof(vt ? "val_policy_frontier" : "policy_frontier", s);
-        if (int rc = launch_policy_frontier(hidden, nsi, (unsigned)plan.waves, plan.ls, s, fa)) return rc;
+        if (int rc = launch_policy_frontier(hidden, nsi, (unsigned)plan.fr.waves, plan.fr.ls, s, fa)) return rc;
         if (fa.spill_budget) {
             ProfScope prof2(vt ? "val_frontier_spill" : "frontier_spill", s);
-            if (int rc = launch_frontier_spill(hidden, nsi, (unsigned)plan.waves, plan.ls, s, fa)) return rc;
+            if (int rc = launch_frontier_spill(hidden, nsi, (unsigned)plan.fr.waves, plan.fr.ls, s, fa)) return rc;
         }
-    } else if (eps->max_len > 0) {
-        dim3 grid((eps->max_len + kChunk - 1) / kChunk, eps->n);
+    } else if (plan.policy != PolicyKernel::TableValu) {
+        // TableSp (with the walk-order job that rides along), TableV3 or TableMfma
         ProfScope prof(vt ? "val_policy_table" : "policy_table", s);
-        const bool valu = table_valu();
-        if (rj_fold) {  // the walk-order job rides along in the state-parallel table
-            if (hidden == 16)
-                launch_table_mfma<16>(arl, nsi, eps->max_len, eps->n, s, *ticks, ep, params, src, eps->inv_min, ctr, cmaps, fills, rew, rj_fold, &rj_done);
-            else
-                launch_table_mfma<32>(arl, nsi, eps->max_len, eps->n, s, *ticks, ep, params, src, eps->inv_min, ctr, cmaps, fills, rew, rj_fold, &rj_done);
-        } else switch (hidden) {
-            case 8: launch_table<8>(arl, nsi, grid, s, *ticks, ep, params, src, eps->inv_min, ctr, cmaps, fills, rew); break;
-            case 16:
-                if (valu) launch_table<16>(arl, nsi, grid, s, *ticks, ep, params, src, eps->inv_min, ctr, cmaps, fills, rew);
-                else launch_table_mfma<16>(arl, nsi, eps->max_len, eps->n, s, *ticks, ep, params, src, eps->inv_min, ctr, cmaps, fills, rew);
-                break;
-            case 32:
-                if (valu) launch_table<32>(arl, nsi, grid, s, *ticks, ep, params, src, eps->inv_min, ctr, cmaps, fills, rew);
-                else launch_table_mfma<32>(arl, nsi, eps->max_len, eps->n, s, *ticks, ep, params, src, eps->inv_min, ctr, cmaps, fills, rew);
-                break;
-            default:
-                if (valu) launch_table<64>(arl, nsi, grid, s, *ticks, ep, params, src, eps->inv_min, ctr, cmaps, fills, rew);
-                else launch_table_mfma<64>(arl, nsi, eps->max_len, eps->n, s, *ticks, ep, params, src, eps->inv_min, ctr, cmaps, fills, rew);
-                break;
+        switch (hidden) {
+            case 16: launch_table_mfma<16>(plan.policy, arl, nsi, eps->max_len, eps->n, SGMM_TABLE_ARGS, rj_fold); break;
+            case 32: launch_table_mfma<32>(plan.policy, arl, nsi, eps->max_len, eps->n, SGMM_TABLE_ARGS, rj_fold); break;
+            default: launch_table_mfma<64>(plan.policy, arl, nsi, eps->max_len, eps->n, SGMM_TABLE_ARGS, rj_fold); break;
+        }
+        SGMM_LAUNCHED();
+    } else {  // TableValu
+        const dim3 grid((eps->max_len + kChunk - 1) / kChunk, eps->n);
+        ProfScope prof(vt ? "val_policy_table" : "policy_table", s);
+        switch (hidden) {
+            case 8: launch_table<8>(arl, nsi, grid, SGMM_TABLE_ARGS); break;
+            case 16: launch_table<16>(arl, nsi, grid, SGMM_TABLE_ARGS); break;
+            case 32: launch_table<32>(arl, nsi, grid, SGMM_TABLE_ARGS); break;
+            default: launch_table<64>(arl, nsi, grid, SGMM_TABLE_ARGS); break;
         }
         SGMM_LAUNCHED();
     }
-    if (fused) {
-        // the frontier launch summed every episode and ran the tail
-    } else if (ProfScope prof(vt ? "val_path_scan" : "path_scan", s); arl) {
-        // 16-wave workgroups while one per CU fits (a 4096-tick segment is one
-        // exact-sum window), 4-wave ones beyond
-        const int nt = eps->n <= kScanArlAt1024 ? kScanThreads : kScanBlock;
-        ep.seq_sum = scan_seq_sum(nt, true, vt) ? 1 : 0;
-        size_t lds = arl_scan_lds(ns);
-        if (step.st) lds = std::max(lds, step_lds_bytes(nt, step));
-        if (nt == kScanThreads)
-            SGMM_LAUNCH(k_path_scan_arl<kScanThreads>, dim3(eps->n), dim3(nt), lds, s, ep, params, eps->inv_min,
-                        nsi, fills, rew, fitness, trades, step);
-        else
-            SGMM_LAUNCH(k_path_scan_arl<kScanBlock>, dim3(eps->n), dim3(nt), lds, s, ep, params, eps->inv_min,
-                        nsi, fills, rew, fitness, trades, step);
-    } else {
-        // the workgroup shrinks as episodes grow: few episodes get a 16-wave
-        // workgroup each (4096-tick windows, the phases spread over the CU);
-        // many get 8- or 4-wave ones (2048- / 1024-tick windows), several
-        // resident per CU, so the serial walks of different episodes overlap
-        // instead of idling the CU (A/B on MI355X: P=64 / 256 / 1024 / 4096)
-        const int nt = scan_threads(eps->n);
-        ep.seq_sum = scan_seq_sum(nt, false, vt) ? 1 : 0;
-        if (fr && lanes_scan(nt, ep.seq_sum != 0, step, src.pop_eps)) {
-            const int lw = lanes_w(eps->n, step);
+#undef SGMM_TABLE_ARGS
+    // (a fused frontier launch summed every episode and ran the tail itself)
+    if (plan.scan != ScanKernel::Fused) {
+        ProfScope prof(vt ? "val_path_scan" : "path_scan", s);
+        const int nt = plan.scan_threads;
+        const dim3 grid(plan.scan_grid), block(nt);
+        ep.seq_sum = plan.seq_sum;
+        if (plan.scan == ScanKernel::Arl) {
+            size_t lds = arl_scan_lds(ns);
+            if (step.st) lds = std::max(lds, step_lds_bytes(nt, step));
+            if (nt == kScanThreads)
+                SGMM_LAUNCH(k_path_scan_arl<kScanThreads>, grid, block, lds, s, ep, params, eps->inv_min,
+                            nsi, fills, rew, fitness, trades, step);
+            else
+                SGMM_LAUNCH(k_path_scan_arl<kScanBlock>, grid, block, lds, s, ep, params, eps->inv_min,
+                            nsi, fills, rew, fitness, trades, step);
+        } else if (plan.scan == ScanKernel::Lanes) {
+            const int lw = plan.lanes_w;
             const size_t lds = lanes_scan_lds(ep.ngrp, lw);
-            const dim3 grid((eps->n + lw - 1) / lw), block(kWave * lw);
 #define SGMM_LANES_LAUNCH(N_, W_)                                                                                 \
     SGMM_LAUNCH((k_path_scan_lanes<N_, W_>), grid, block, lds, s, ep, params, eps->inv_min, cmaps,                \
                 reinterpret_cast<const uint32_t*>(ctr), kinfo, rew, fitness, trades, step, eps->n)
@@ -2835,44 +2570,34 @@ static int rollout_impl(const sgmm_ticks* ticks, const sgmm_episodes* eps,
                 else SGMM_LANES_LAUNCH(8, 4);
             }
 #undef SGMM_LANES_LAUNCH
-        } else if (size_t lds = (size_t)(nt == kWave ? 4 * kWave : nt) * kSumTpt * sizeof(double) +  // the window
-                                (fr ? (size_t)5 * kFrontierLanes * ep.ngrp : 0);  // chunk start states + merge info
-                   fr) {
-            if (step.st) lds = std::max(lds, step_lds_bytes(nt, step));
-            if (nsi <= 5)
-                launch_path_scan<5, true>(nt, eps->n, lds, s, ep, params, eps->inv_min, cmaps, ctr, kinfo, rew,
-                                          fitness, trades, step);
-            else
-                launch_path_scan<8, true>(nt, eps->n, lds, s, ep, params, eps->inv_min, cmaps, ctr, kinfo, rew,
-                                          fitness, trades, step);
-        } else if (nsi <= 5) {
-            if (step.st) lds = std::max(lds, step_lds_bytes(nt, step));
-            launch_path_scan<5, false>(nt, eps->n, lds, s, ep, params, eps->inv_min, cmaps, ctr, kinfo, rew,
-                                       fitness, trades, step);
         } else {
+            size_t lds = (size_t)(nt == kWave ? 4 * kWave : nt) * kSumTpt * sizeof(double) +  // the window
+                         (fr ? (size_t)5 * kFrontierLanes * ep.ngrp : 0);  // chunk start states + merge info
             if (step.st) lds = std::max(lds, step_lds_bytes(nt, step));
-            launch_path_scan<8, false>(nt, eps->n, lds, s, ep, params, eps->inv_min, cmaps, ctr, kinfo, rew,
-                                       fitness, trades, step);
+#define SGMM_WAVE_SCAN(N_, FR_)                                                                                   \
+    launch_path_scan<N_, FR_>(nt, eps->n, lds, s, ep, params, eps->inv_min, cmaps, ctr, kinfo, rew, fitness, trades, step)
+            if (fr) {
+                if (nsi <= 5) SGMM_WAVE_SCAN(5, true);
+                else SGMM_WAVE_SCAN(8, true);
+            } else {
+                if (nsi <= 5) SGMM_WAVE_SCAN(5, false);
+                else SGMM_WAVE_SCAN(8, false);
+            }
+#undef SGMM_WAVE_SCAN
         }
     }
     SGMM_LAUNCHED();
-    if (fr && step.st && step.mode == 3 && walk_reorder(eps, plan, src, walk_order)) {
-        ReorderJob job{wslots, walk_order, eps->n, plan.whole, plan.gtail, src.pop_eps};
-        job.len = eps->max_len;  // equal-length episodes (walk_reorder)
-        if (const int w = plan_value(SGMM_PLAN_REORDER_WEIGHTS); w > 0 && (w >> 8) > 0 && (w & 255) > 0) {
-            job.w_whole = (uint32_t)(w >> 8) & 63u;
-            job.w_split = (uint32_t)w & 63u;
-        }
+    if (plan.reorder) {
+        ReorderJob job{wslots, walk_order, eps->n, plan.fr.whole, plan.fr.gtail, src.pop_eps};
+        job.w_whole = plan.w_whole;
+        job.w_split = plan.w_split;
+        job.len = eps->max_len;  // equal-length episodes (LaunchPlan::reorder)
         if (rj_out) {
             *rj_out = job;
         } else {
             SGMM_LAUNCH(k_walk_reorder, dim3(1), dim3(kScanThreads), 0, s, job);
             SGMM_LAUNCHED();
         }
-    }
-    if (rj_in && rj_in->order && !rj_done) {  // (not reached: a job that cannot ride along ran first)
-        set_error("walk-order job neither folded nor launched");
-        return SGMM_ERR_ARG;
     }
     return SGMM_OK;
 }
@@ -2888,7 +2613,7 @@ extern "C" int sgmm_rollout_fitness(const sgmm_ticks* ticks, const sgmm_episodes
     const bool arl = adv_genomes != nullptr;
     SGMM_REQUIRE(!arl || adv_stride >= kAdvParams, "adv_stride < 74");
     const GenomeSrc src{mm_genomes, mm_stride, adv_genomes, adv_stride, nullptr, nullptr, nullptr, 0, 0};
-    return rollout_impl(ticks, eps, params, src, arl, hidden, fitness, trades, workspace,
+    return rollout_impl(plan_knobs(), ticks, eps, params, src, arl, hidden, fitness, trades, workspace,
                         workspace_bytes, StepArgs{}, as_stream(stream));
 }
 
@@ -2903,7 +2628,7 @@ extern "C" int sgmm_rollout_fitness_asked(const sgmm_ticks* ticks, const sgmm_ep
     SGMM_REQUIRE(pop->i0 >= 0, "negative i0");
     const bool arl = pop->master_adv != nullptr;
     const GenomeSrc src{nullptr, 0, nullptr, 0, pop->state, pop->master_mm, pop->master_adv, pop->seed, pop->i0};
-    return rollout_impl(ticks, eps, params, src, arl, hidden, fitness, trades, workspace,
+    return rollout_impl(plan_knobs(), ticks, eps, params, src, arl, hidden, fitness, trades, workspace,
                         workspace_bytes, StepArgs{}, as_stream(stream));
 }
 
@@ -2920,10 +2645,24 @@ extern "C" int sgmm_generation(const sgmm_ticks* ticks, const sgmm_episodes* eps
     const int64_t n_mm = (int64_t)hidden * hidden + 7 * hidden + 2;
     SGMM_REQUIRE(n_mm <= kMaxStepParams, "genome too large for the fused GA step");
     const bool arl = master_adv != nullptr;
-    const GenomeSrc src{nullptr, 0, nullptr, 0, state, master_mm, master_adv, seed, 0};
-    StepArgs step{state, master_mm, master_adv, best_master, n_mm, arl ? 1250 : 0, seed, history,
-                  history_cap, P};
-    return rollout_impl(ticks, eps, params, src, arl, hidden, fitness, trades, workspace,
+    // one population, its key by value: no per-population strides or seeds
+    GenomeSrc src{};
+    src.st = state;
+    src.master_mm = master_mm;
+    src.master_adv = master_adv;
+    src.seed = seed;
+    StepArgs step{};
+    step.st = state;
+    step.master_mm = master_mm;
+    step.master_adv = master_adv;
+    step.best_master = best_master;
+    step.n_mm = n_mm;
+    step.n_adv = arl ? kAdvGenome : 0;
+    step.seed = seed;
+    step.history = history;
+    step.hist_cap = history_cap;
+    step.P = P;
+    return rollout_impl(plan_knobs(), ticks, eps, params, src, arl, hidden, fitness, trades, workspace,
                         workspace_bytes, step, as_stream(stream));
 }
 
@@ -2934,6 +2673,49 @@ static int check_pops(const sgmm_populations* pops) {
     SGMM_REQUIRE(pops->states && pops->masters_mm && pops->seeds, "null states / masters / seeds");
     SGMM_REQUIRE(pops->history_cap >= 0 && (pops->history || pops->history_cap == 0), "history");
     return SGMM_OK;
+}
+
+static int64_t pops_n_mm(const sgmm_populations* pops) {
+    return (int64_t)pops->hidden * pops->hidden + 7 * pops->hidden + 2;
+}
+
+// The asked genomes of K populations: pop_eps episodes per population,
+// individual i0 + genome[e] of the episode's population -- or (use_best) its
+// tell's argmax, rolled out against no adversary (the deferred validation).
+static GenomeSrc pops_src(const sgmm_populations* pops, int32_t pop_eps, int32_t i0, bool use_best) {
+    const bool adv = pops->masters_adv != nullptr && !use_best;
+    GenomeSrc src{};
+    src.st = pops->states;
+    src.master_mm = pops->masters_mm;
+    src.master_adv = adv ? pops->masters_adv : nullptr;
+    src.i0 = i0;
+    src.pop_eps = pop_eps;
+    src.seeds = pops->seeds;
+    src.mm_pstride = pops_n_mm(pops);
+    src.adv_pstride = adv ? kAdvGenome : 0;
+    src.use_best = use_best ? 1 : 0;
+    return src;
+}
+
+// The generation tail of K populations of P individuals, pop_eps episodes per
+// population in this launch (StepArgs::mode).  Mode 2, the validation
+// bookkeeping alone, touches no adversary master.
+static StepArgs pops_step(const sgmm_populations* pops, int32_t P, int32_t pop_eps, int32_t mode) {
+    const bool adv = pops->masters_adv != nullptr && mode != 2;
+    StepArgs step{};
+    step.st = pops->states;
+    step.master_mm = pops->masters_mm;
+    step.master_adv = adv ? pops->masters_adv : nullptr;
+    step.best_master = pops->best_masters;
+    step.n_mm = pops_n_mm(pops);
+    step.n_adv = adv ? kAdvGenome : 0;
+    step.history = pops->history;
+    step.hist_cap = pops->history_cap;
+    step.P = P;
+    step.pop_eps = pop_eps;
+    step.seeds = pops->seeds;
+    step.mode = mode;
+    return step;
 }
 
 extern "C" int sgmm_generation_multi(const sgmm_ticks* ticks, const sgmm_episodes* eps,
@@ -2947,19 +2729,10 @@ extern "C" int sgmm_generation_multi(const sgmm_ticks* ticks, const sgmm_episode
     SGMM_REQUIRE((int64_t)eps->n == 2LL * K * P,
                  "episodes must be n_pop x (P training + P validation) = %lld, got %d",
                  2LL * K * P, eps->n);
-    const int64_t n_mm = (int64_t)H * H + 7 * H + 2;
-    SGMM_REQUIRE(n_mm <= kMaxStepParams, "genome too large for the fused GA step");
-    const bool arl = pops->masters_adv != nullptr;
-    const int64_t n_adv = arl ? kAdvGenome : 0;
-    GenomeSrc src{nullptr, 0, nullptr, 0, pops->states, pops->masters_mm, pops->masters_adv, 0, 0};
-    src.pop_eps = 2 * P;
-    src.seeds = pops->seeds;
-    src.mm_pstride = n_mm;
-    src.adv_pstride = n_adv;
-    StepArgs step{pops->states, pops->masters_mm, pops->masters_adv, pops->best_masters, n_mm, n_adv, 0,
-                  pops->history, pops->history_cap, P, 2 * P, pops->seeds};
-    return rollout_impl(ticks, eps, params, src, arl, H, fitness, trades, workspace, workspace_bytes, step,
-                        as_stream(stream));
+    SGMM_REQUIRE(pops_n_mm(pops) <= kMaxStepParams, "genome too large for the fused GA step");
+    return rollout_impl(plan_knobs(), ticks, eps, params, pops_src(pops, 2 * P, 0, false),
+                        pops->masters_adv != nullptr, H, fitness, trades, workspace, workspace_bytes,
+                        pops_step(pops, P, 2 * P, 0), as_stream(stream));
 }
 
 // Validation of every population's post-tell master (drl_engine.py:129-160):
@@ -2969,28 +2742,19 @@ extern "C" int sgmm_generation_multi(const sgmm_ticks* ticks, const sgmm_episode
 // deferred: the training launch's tail ran the tell's argmax only (StepArgs
 // mode 3); episode k rolls out population k's best individual from the
 // pre-tell master and the scan's workgroup k writes the new master (mode 4)
-static int validate_impl(const sgmm_ticks* ticks, const sgmm_episodes* val_eps, const sgmm_env_params* params,
-                         const sgmm_populations* pops, double* val_fitness, int32_t* val_trades, void* workspace,
-                         size_t workspace_bytes, hipStream_t s, bool deferred = false,
-                         const ReorderJob* rj = nullptr) {
+static int validate_impl(const PlanKnobs& knobs, const sgmm_ticks* ticks, const sgmm_episodes* val_eps,
+                         const sgmm_env_params* params, const sgmm_populations* pops, double* val_fitness,
+                         int32_t* val_trades, void* workspace, size_t workspace_bytes, hipStream_t s,
+                         bool deferred = false, const ReorderJob* rj = nullptr) {
     const int32_t H = pops->hidden, K = pops->n_pop;
     if (int rc = check_episodes(ticks, val_eps, params, pops->masters_mm, H)) return rc;
     SGMM_REQUIRE(val_eps->n == K, "validation episodes must be one per population (%d), got %d", K, val_eps->n);
-    const int64_t n_mm = (int64_t)H * H + 7 * H + 2;
-    const bool arl = pops->masters_adv != nullptr;
-    GenomeSrc src{pops->masters_mm, n_mm, nullptr, 0, nullptr, nullptr, nullptr, 0, 0};
-    if (deferred) {
-        src = GenomeSrc{nullptr, 0, nullptr, 0, pops->states, pops->masters_mm, nullptr, 0, 0};
-        src.pop_eps = 1;
-        src.seeds = pops->seeds;
-        src.mm_pstride = n_mm;
-        src.use_best = 1;
-    }
-    StepArgs step{pops->states, pops->masters_mm, (deferred && arl) ? pops->masters_adv : nullptr, pops->best_masters,
-                  n_mm, (deferred && arl) ? (int64_t)kAdvGenome : 0, 0, pops->history, pops->history_cap, 1, 1,
-                  pops->seeds, deferred ? 4 : 2};
-    return rollout_impl(ticks, val_eps, params, src, false, H, val_fitness, val_trades, workspace, workspace_bytes,
-                        step, s, nullptr, rj);
+    GenomeSrc src{};  // the post-tell masters as materialized rows
+    src.mm = pops->masters_mm;
+    src.mm_stride = pops_n_mm(pops);
+    if (deferred) src = pops_src(pops, 1, 0, true);
+    return rollout_impl(knobs, ticks, val_eps, params, src, false, H, val_fitness, val_trades, workspace,
+                        workspace_bytes, pops_step(pops, 1, 1, deferred ? 4 : 2), s, nullptr, rj);
 }
 
 extern "C" int sgmm_validate_multi(const sgmm_ticks* ticks, const sgmm_episodes* val_eps,
@@ -2999,8 +2763,8 @@ extern "C" int sgmm_validate_multi(const sgmm_ticks* ticks, const sgmm_episodes*
                                    size_t workspace_bytes, void* stream) {
     clear_error();
     if (int rc = check_pops(pops)) return rc;
-    return validate_impl(ticks, val_eps, params, pops, val_fitness, val_trades, workspace, workspace_bytes,
-                         as_stream(stream));
+    return validate_impl(plan_knobs(), ticks, val_eps, params, pops, val_fitness, val_trades, workspace,
+                         workspace_bytes, as_stream(stream));
 }
 
 extern "C" int sgmm_generation_multi_best(const sgmm_ticks* ticks, const sgmm_episodes* train_eps,
@@ -3016,22 +2780,13 @@ extern "C" int sgmm_generation_multi_best(const sgmm_ticks* ticks, const sgmm_ep
                  (int64_t)K * P, train_eps->n);
     SGMM_REQUIRE(val_eps && val_eps->n == K, "validation episodes must be one per population");
     SGMM_REQUIRE(val_fitness && val_trades, "null validation outputs");
-    const int64_t n_mm = (int64_t)H * H + 7 * H + 2;
-    SGMM_REQUIRE(n_mm <= kMaxStepParams, "genome too large for the fused GA step");
-    const bool arl = pops->masters_adv != nullptr;
-    const int64_t n_adv = arl ? kAdvGenome : 0;
-    GenomeSrc src{nullptr, 0, nullptr, 0, pops->states, pops->masters_mm, pops->masters_adv, 0, 0};
-    src.pop_eps = P;
-    src.seeds = pops->seeds;
-    src.mm_pstride = n_mm;
-    src.adv_pstride = n_adv;
-    StepArgs step{pops->states, pops->masters_mm, pops->masters_adv, pops->best_masters, n_mm, n_adv, 0,
-                  pops->history, pops->history_cap, P, P, pops->seeds, 3};
+    SGMM_REQUIRE(pops_n_mm(pops) <= kMaxStepParams, "genome too large for the fused GA step");
+    const PlanKnobs knobs = plan_knobs();  // one snapshot for both launches
     // the validation batch is checked before anything is enqueued
     if (int rc = check_episodes(ticks, val_eps, params, pops->masters_mm, H)) return rc;
     {
         const int32_t vnsi = val_eps->inv_max - val_eps->inv_min + 1;
-        const size_t vneed = rollout_ws_bytes(val_eps->n, val_eps->total_steps, vnsi, false);
+        const size_t vneed = rollout_ws_bytes(val_eps->n, val_eps->total_steps, vnsi, false, knobs);
         if (val_eps->n > 0 && (!workspace || workspace_bytes < vneed)) {
             set_error("workspace %zu bytes < required %zu (validation batch)", workspace_bytes, vneed);
             return SGMM_ERR_WORKSPACE;
@@ -3043,11 +2798,12 @@ extern "C" int sgmm_generation_multi_best(const sgmm_ticks* ticks, const sgmm_ep
     // (the feedback rewrites it); train_eps itself is only read
     sgmm_episodes tr = *train_eps;
     if (pops->walk_order) tr.order = pops->walk_order;
-    if (int rc = rollout_impl(ticks, &tr, params, src, arl, H, fitness, trades, workspace, workspace_bytes,
-                              step, s, &job, nullptr, pops->walk_order))
+    if (int rc = rollout_impl(knobs, ticks, &tr, params, pops_src(pops, P, 0, false), pops->masters_adv != nullptr, H,
+                              fitness, trades, workspace, workspace_bytes, pops_step(pops, P, P, 3), s, &job, nullptr,
+                              pops->walk_order))
         return rc;
-    return validate_impl(ticks, val_eps, params, pops, val_fitness, val_trades, workspace, workspace_bytes, s, true,
-                         &job);
+    return validate_impl(knobs, ticks, val_eps, params, pops, val_fitness, val_trades, workspace, workspace_bytes, s,
+                         true, &job);
 }
 
 extern "C" int sgmm_rollout_fitness_asked_multi(const sgmm_ticks* ticks, const sgmm_episodes* eps,
@@ -3062,13 +2818,8 @@ extern "C" int sgmm_rollout_fitness_asked_multi(const sgmm_ticks* ticks, const s
     if (int rc = check_episodes(ticks, eps, params, pops->masters_mm, H)) return rc;
     SGMM_REQUIRE(i0 >= 0 && n_eps_pop > 0 && (int64_t)eps->n == (int64_t)K * n_eps_pop,
                  "episodes must be n_pop x n_eps_pop (i0=%d, n_eps_pop=%d, n=%d)", i0, n_eps_pop, eps->n);
-    const bool arl = pops->masters_adv != nullptr;
-    GenomeSrc src{nullptr, 0, nullptr, 0, pops->states, pops->masters_mm, pops->masters_adv, 0, i0};
-    src.pop_eps = n_eps_pop;
-    src.seeds = pops->seeds;
-    src.mm_pstride = (int64_t)H * H + 7 * H + 2;
-    src.adv_pstride = arl ? kAdvGenome : 0;
-    return rollout_impl(ticks, eps, params, src, arl, H, fitness, trades, workspace, workspace_bytes,
+    return rollout_impl(plan_knobs(), ticks, eps, params, pops_src(pops, n_eps_pop, i0, false),
+                        pops->masters_adv != nullptr, H, fitness, trades, workspace, workspace_bytes,
                         StepArgs{}, as_stream(stream));
 }
 
@@ -3090,7 +2841,7 @@ extern "C" int sgmm_rollout_trace(const sgmm_ticks* ticks, const sgmm_episodes* 
     const int32_t nsi = eps->inv_max - eps->inv_min + 1;
     TraceOut o{off_a, off_b, adv_a, adv_b, inventory, cash, reward, pnl_reward, fee_paid,
                fill_buy, fill_sell, raw_a, raw_b, fitness, trades};
-    const EpArrays ep = ep_arrays(eps, arl);
+    const EpArrays ep = ep_arrays(eps, arl, workspace_layout(eps->n, eps->total_steps, nsi, arl, simd_count(), plan_knobs()).rs);
     hipStream_t s = as_stream(stream);
     ProfScope prof("rollout_direct", s);
     switch (hidden) {
