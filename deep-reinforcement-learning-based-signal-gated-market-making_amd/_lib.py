@@ -88,7 +88,22 @@ class GAHistory(ctypes.Structure):
                 ("flags", ctypes.c_int32)]
 
 
+class QuoteRule(ctypes.Structure):
+    """sgmm_quote_rule: an inventory-indexed quote table (FOIC / GLFT)."""
+    _fields_ = [("mode", ctypes.c_int32), ("n_inventory", ctypes.c_int32), ("quote_tick", ctypes.c_double),
+                ("ask", ctypes.c_double * 8), ("bid", ctypes.c_double * 8)]
+
+
+class EpisodeSummary(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in ("total_pnl", "map", "pnl_to_map", "max_dd", "sharpe_trades",
+                                               "sharpe_steps", "pnl_to_map_floor", "fitness", "final_cash")] + \
+        [(n, ctypes.c_int32) for n in ("trade_rows", "fills_buy", "fills_sell", "final_inventory", "steps",
+                                       "reserved")]
+
+
 assert ctypes.sizeof(EnvParams) == 48
+assert ctypes.sizeof(QuoteRule) == 144
+assert ctypes.sizeof(EpisodeSummary) == 96
 assert ctypes.sizeof(GAState) == 80
 assert ctypes.sizeof(GAHistory) == 40
 assert ctypes.sizeof(Populations) == 72
@@ -110,6 +125,10 @@ SIGNATURES = {
                                             _VP, _I64, _I32, _VP, _I64, _VP, _VP, _VP, _SZ, _VP]),
     "sgmm_rollout_trace": (ctypes.c_int, [ctypes.POINTER(Ticks), ctypes.POINTER(Episodes), _VP,
                                           _VP, _I64, _I32, _VP, _I64] + [_VP] * 16),
+    "sgmm_rollout_summary": (ctypes.c_int, [ctypes.POINTER(Ticks), ctypes.POINTER(Episodes), _VP,
+                                            _VP, _I64, _I32, _VP, _VP, _I32, _VP, _VP]),
+    "sgmm_rule_trace": (ctypes.c_int, [ctypes.POINTER(Ticks), ctypes.POINTER(Episodes), _VP,
+                                       _VP, _VP, _I32] + [_VP] * 12),
     "sgmm_ga_ask": (ctypes.c_int, [_VP, _I64, _VP, _U32, _U64, _I32, _I32, _VP, _I64, _VP]),
     "sgmm_ga_state_init": (ctypes.c_int, [_VP, _D, _I32, _D, _VP]),
     "sgmm_ga_tell": (ctypes.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I64, _VP, _VP, _I64, _I64,

@@ -16,6 +16,9 @@ Schemas:
               off_a, off_b, action, reward, inventory, cash, fee_paid,
               s1_pred, s2_pred) updated with FTPEnv.step's info
   "blind"     agent_trainer.py:139-155 -- StrategyRecorder.record's 13 columns
+The benchmark strategies' backtests (main.py:99-132 run_benchmark_and_save)
+take the same route through sgmm_rule_trace: run_rule_backtests /
+run_benchmark_and_save, "backtest" schema.
 (pipeline/evaluator.py's record_detailed path raises KeyError('ask') in the
 reference, Env/recorder.py:19-45, so it has no frame to mirror.)
 """
@@ -90,6 +93,67 @@ def _frame(schema, cols, bundle, phi):
     return df
 
 
+def _device_batch(bundles, train_stats, phis, ticks_, fees, dev):
+    """The request's distinct bundles as one device TickStore, one params row
+    per backtest, and each backtest's (tick offset, length)."""
+    ts = TickStore()
+    seg_of = {}
+    seg = []
+    for b in bundles:
+        if id(b) not in seg_of:
+            seg_of[id(b)] = ts.add(b, train_stats)
+        seg.append(ts.segments[seg_of[id(b)]])
+    ts.to(dev)
+    params = params_tensor([EnvConfig(phi=p, tick_size=t, fee_rate=f) for p, t, f in zip(phis, ticks_, fees)], dev)
+    return ts, params, seg
+
+
+def _split_frames(schema, host, eps, bundles, phis):
+    out = []
+    for e in range(eps.n):
+        a, T = int(eps.step_off[e]), int(eps.length[e])
+        out.append(_frame(schema, {k: v[a:a + T] for k, v in host.items()}, bundles[e], float(phis[e])))
+    return out
+
+
+# signals do not enter a quote rule: without train_stats they are stored unscaled
+_NO_STATS = {"s1_m": 0.0, "s1_s": 1.0, "s2_m": 0.0, "s2_s": 1.0}
+
+
+def run_rule_backtests(rules, bundles, phis, fee_rates=0.0, tick_size=0.001, train_stats=None, device="cuda"):
+    """Backtest every (quote rule, bundle, phi, fee) in one sgmm_rule_trace
+    launch (main.py:99-132, batched).  rules: sgmm_quote_rule records
+    (benchmarks.quote_rule) sharing one inventory range; the other arguments
+    broadcast as in run_backtests.  Returns one "backtest"-schema DataFrame per
+    rule."""
+    rules = np.stack([np.asarray(r) for r in rules]) if isinstance(rules, (list, tuple)) else np.atleast_1d(rules)
+    n = len(rules)
+    if n == 0:
+        return []
+    bundles = _broadcast(bundles, n, "bundle")
+    phis, fees, ticks_ = (_broadcast(v, n, k) for v, k in ((phis, "phis"), (fee_rates, "fee_rates"),
+                                                          (tick_size, "tick_size")))
+    dev = torch.device(device)
+    ts, params, seg = _device_batch(bundles, train_stats or _NO_STATS, phis, ticks_, fees, dev)
+    eps = EpisodeBatch(np.arange(n), [s[0] for s in seg], [s[1] for s in seg], np.arange(n)).to(dev)
+    _, _, tr = RolloutEngine(dev).trace_rules(ts, eps, params, rules)
+    return _split_frames("backtest", {k: v.cpu().numpy() for k, v in tr.items()}, eps, bundles, phis)
+
+
+def run_benchmark_and_save(strategy_name, policy, bundle, phi_param, fee_rate, save_dir, train_stats):
+    """main.py:99-132: backtest a benchmark strategy at tick 0.001 ('glft'
+    quotes mid-relative prices, anything else tick offsets), write
+    {save_dir}/backtest_{phi_param}.parquet, return the frame."""
+    from .benchmarks import quote_rule, rule_mode
+    rule = quote_rule(policy, quote_tick=0.001, mode=rule_mode(strategy_name))
+    df = run_rule_backtests([rule], bundle, phi_param, fee_rate, 0.001, train_stats)[0]
+    save_path = f"{save_dir}/backtest_{phi_param}.parquet"
+    os.makedirs(save_dir, exist_ok=True)
+    df.to_parquet(save_path, index=False)
+    print(f"Success: {strategy_name} benchmark completed.")
+    return df
+
+
 def run_backtests(policies, bundles, train_stats, phis, fee_rates=0.0, tick_size=0.001,
                   schema="backtest", device="cuda"):
     """Backtest every (policy, bundle, phi, fee) in one device launch.
@@ -111,25 +175,11 @@ def run_backtests(policies, bundles, train_stats, phis, fee_rates=0.0, tick_size
     phis, fees, ticks_ = (_broadcast(v, n, k) for v, k in ((phis, "phis"), (fee_rates, "fee_rates"),
                                                           (tick_size, "tick_size")))
     dev = torch.device(device)
-    ts = TickStore()
-    seg_of = {}
-    seg = []
-    for b in bundles:
-        if id(b) not in seg_of:
-            seg_of[id(b)] = ts.add(b, train_stats)
-        seg.append(ts.segments[seg_of[id(b)]])
-    ts.to(dev)
-    params = params_tensor([EnvConfig(phi=p, tick_size=t, fee_rate=f) for p, t, f in zip(phis, ticks_, fees)], dev)
+    ts, params, seg = _device_batch(bundles, train_stats, phis, ticks_, fees, dev)
     eps = EpisodeBatch(np.arange(n), [s[0] for s in seg], [s[1] for s in seg], np.arange(n)).to(dev)
     mm = torch.from_numpy(np.stack(genomes)).to(dev)
     _, _, tr = RolloutEngine(dev).trace(ts, eps, params, mm, H)
-    host = {k: v.cpu().numpy() for k, v in tr.items()}
-    out = []
-    for e in range(n):
-        a, T = int(eps.step_off[e]), int(eps.length[e])
-        cols = {k: v[a:a + T] for k, v in host.items()}
-        out.append(_frame(schema, cols, bundles[e], float(phis[e])))
-    return out
+    return _split_frames(schema, {k: v.cpu().numpy() for k, v in tr.items()}, eps, bundles, phis)
 
 
 def run_drl_backtest(symbol, method_name, weight_path, bundle, phi, fee_rate, train_stats):

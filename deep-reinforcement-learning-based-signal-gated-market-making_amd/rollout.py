@@ -16,12 +16,19 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import EnvParams, Episodes, Ticks, check, ptr, stream_ptr
+from ._lib import EnvParams, EpisodeSummary, Episodes, QuoteRule, Ticks, check, ptr, stream_ptr
 
 ENV_PARAMS_DTYPE = np.dtype([("phi", "<f8"), ("tick", "<f8"), ("fee", "<f8"),
                              ("idle_penalty", "<f8"), ("i_max", "<i4"), ("i_min", "<i4"),
                              ("act_scale", "<f4"), ("adv_scale", "<f4")])
 assert ENV_PARAMS_DTYPE.itemsize == ctypes.sizeof(EnvParams)
+
+SUMMARY_DTYPE = np.dtype([(k, "<f8") for k in ("total_pnl", "map", "pnl_to_map", "max_dd", "sharpe_trades",
+                                               "sharpe_steps", "pnl_to_map_floor", "fitness", "final_cash")] +
+                         [(k, "<i4") for k in ("trade_rows", "fills_buy", "fills_sell", "final_inventory",
+                                               "steps", "reserved")])
+assert SUMMARY_DTYPE.itemsize == ctypes.sizeof(EpisodeSummary) == 96
+RULE_TRACE_COLUMNS = ("off_a", "off_b", "inventory", "cash", "reward", "pnl", "fee_paid", "fill_buy", "fill_sell")
 
 COLUMNS = ("s1n", "s2n", "mid_next", "best_ask", "best_bid", "buy_max", "sell_min")
 
@@ -204,6 +211,60 @@ class RolloutEngine:
                                    "raw_a", "raw_b")],
             ptr(fit), ptr(trd), stream_ptr(stream))
         check(rc, "sgmm_rollout_trace")
+        return fit, trd, tr
+
+
+    def _rules(self, rules, eps):
+        """Host rule records (QUOTE_RULE_DTYPE) -> (host copy kept alive, device bytes, count)."""
+        host = np.ascontiguousarray(np.atleast_1d(rules))
+        if host.dtype.itemsize != ctypes.sizeof(QuoteRule) or host.ndim != 1 or len(host) == 0:
+            raise ValueError("rules: a non-empty 1-d array of sgmm_quote_rule records (benchmarks.quote_rule)")
+        if eps.n and not (0 <= eps.genome.min() and eps.genome.max() < len(host)):
+            raise ValueError(f"episode rule indices must lie in [0, {len(host)})")
+        # the device copy stays referenced until the next call: the launch reads it
+        self._rules_dev = torch.from_numpy(host.view(np.uint8).copy()).to(self.device)
+        return host, self._rules_dev, len(host)
+
+    def summary(self, ticks: TickStore, eps: EpisodeBatch, params: torch.Tensor, mm: torch.Tensor | None = None,
+                hidden: int | None = None, rules=None, stream=None):
+        """Per-episode summary (sgmm_rollout_summary), nothing traced: exactly one
+        of ``mm`` (TradingPolicy genome rows, with ``hidden``) and ``rules`` (host
+        records from benchmarks.quote_rule; eps.genome indexes them).  Returns the
+        device tensor (E x 96 bytes) and its host copy as a SUMMARY_DTYPE array
+        (the copy waits for the launch)."""
+        if (mm is None) == (rules is None):
+            raise ValueError("exactly one of mm / rules must be given")
+        out = torch.empty((eps.n, SUMMARY_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        tk, ep = ticks.struct(), eps.struct()
+        if rules is not None:
+            host, dev, n = self._rules(rules, eps)
+            rc = self.L.sgmm_rollout_summary(ctypes.byref(tk), ctypes.byref(ep), ptr(params), None, 0, 0,
+                                             ptr(dev), host.ctypes.data, n, ptr(out), stream_ptr(stream))
+        else:
+            # a one-row tensor may report any row stride: its row length is the safe one
+            stride = mm.stride(0) if mm.shape[0] > 1 else mm.shape[1]
+            rc = self.L.sgmm_rollout_summary(ctypes.byref(tk), ctypes.byref(ep), ptr(params), ptr(mm),
+                                             stride, int(hidden or 0), None, None, 0, ptr(out),
+                                             stream_ptr(stream))
+        check(rc, "sgmm_rollout_summary")
+        if stream is not None:  # the copy below runs on the current stream
+            stream.synchronize()
+        return out, out.cpu().numpy().reshape(-1).view(SUMMARY_DTYPE)
+
+    def trace_rules(self, ticks: TickStore, eps: EpisodeBatch, params: torch.Tensor, rules, stream=None):
+        """Per-step trace of rule episodes (sgmm_rule_trace): (fitness, trades,
+        dict of device columns RULE_TRACE_COLUMNS, rows step_off[e]+t)."""
+        n, dv = eps.total_steps, self.device
+        tr = {k: torch.empty(n, dtype=dt, device=dv) for k, dt in zip(
+            RULE_TRACE_COLUMNS, (torch.int32,) * 3 + (torch.float64,) * 4 + (torch.uint8,) * 2)}
+        fit = torch.empty(eps.n, dtype=torch.float64, device=dv)
+        trd = torch.empty(eps.n, dtype=torch.int32, device=dv)
+        host, dev, nr = self._rules(rules, eps)
+        tk, ep = ticks.struct(), eps.struct()
+        rc = self.L.sgmm_rule_trace(ctypes.byref(tk), ctypes.byref(ep), ptr(params), ptr(dev), host.ctypes.data,
+                                    nr, *[ptr(tr[k]) for k in RULE_TRACE_COLUMNS], ptr(fit), ptr(trd),
+                                    stream_ptr(stream))
+        check(rc, "sgmm_rule_trace")
         return fit, trd, tr
 
 

@@ -163,6 +163,89 @@ int sgmm_rollout_trace(const sgmm_ticks *ticks, const sgmm_episodes *eps,
                        float *raw_a, float *raw_b,
                        double *fitness, int32_t *trades, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Strategy evaluation: the benchmark strategies as policies, and per-episode
+ * summaries without a trace (main.py:99-132, 206-210, 300-324;
+ * analytics/mm_analyzer.py:5-56).
+ * ------------------------------------------------------------------------ */
+
+/* An inventory-indexed quote rule: the action is a function of the current
+ * inventory and the tick's best ask / bid, no MLP (Env/benchmarks.py through
+ * main.py:104-113).  The host evaluates the strategy's get_action(inventory)
+ * for every inventory value (pow / log / sqrt stay there); the device does the
+ * per-tick arithmetic, all float64, unfused, with q = inventory - inv_min:
+ *   mode 0 (main.py:113, FOIC)   off_a = (int)rint(ask[q]), off_b = (int)rint(bid[q])
+ *   mode 1 (main.py:106-111, GLFT)
+ *       mid_p = (best_ask + best_bid) / 2.0
+ *       off_a = (int)rint(((mid_p + ask[q]) - best_ask) / quote_tick)
+ *       off_b = (int)rint((best_bid - (mid_p - bid[q])) / quote_tick)
+ * rint rounds half to even (np.round); the conversion to int32 saturates and
+ * maps NaN to INT32_MIN.  The reference converts to a 64-bit int, so rounded
+ * offsets outside the int32 range are outside the parity domain. */
+typedef struct sgmm_quote_rule {      /* one rule = one "genome" row */
+    int32_t mode;                     /* 0: tick offsets, 1: mid-relative price offsets */
+    int32_t n_inventory;              /* entries used, = inv_max - inv_min + 1, <= 8 */
+    double  quote_tick;               /* mode 1: the divisor of main.py:109-110 (0.001 there) */
+    double  ask[8], bid[8];           /* indexed by inventory - inv_min */
+} sgmm_quote_rule;                    /* 144 bytes */
+
+/* What StrategyAnalytics.summary_dict (analytics/mm_analyzer.py:12-56) and
+ * get_clean_stats (main.py:309-324) report of one backtest frame, with
+ * w[t] = cash_t + inventory_t * mid[t] after step t (the recorder's wealth,
+ * Env/recorder.py:46) and T = steps:
+ *   total_pnl = w[T-1] - w[0];  max_dd = min_t (w[t] - max_{u<=t} w[u]);
+ *   map = (sum_t |inventory_t|) / T (integer sum);
+ *   pnl_to_map = map == 0 ? 0 : total_pnl / map;
+ *   pnl_to_map_floor = total_pnl / max(map, 1e-2);
+ *   trade_rows = steps with a fill on either side, fills_* the per-side sums;
+ *   sharpe_trades: over the wealth differences between consecutive trade rows,
+ *     0 with fewer than 2 trade rows, NaN with exactly 2, 0 if std == 0, else
+ *     mean / std (ddof = 1);
+ *   sharpe_steps = mean(dw) / (std(dw, ddof = 1) + 1e-9) over the T-1 step
+ *     differences (NaN for T <= 2);
+ *   fitness = the reward sum in sequential order, minus idle_penalty when
+ *     trade_rows == 0 (sgmm_rollout_fitness's value); final_cash /
+ *     final_inventory = the last cash_t / inventory_t.
+ * Every field but the two Sharpes is accumulated in the reference's
+ * sequential float64 order and is bit-exact.  The Sharpes use one pass of
+ * shifted sums (shift = the first difference x0: s = sum (x - x0), ss = sum
+ * (x - x0)^2, mean = x0 + s / n, var = max(ss - s * s / n, 0) / (n - 1)),
+ * within 1e-9 relative of the reference's two-pass value.  An episode of
+ * length 0 reports zeros (NaN sharpe_steps). */
+typedef struct sgmm_episode_summary {
+    double total_pnl, map, pnl_to_map, max_dd, sharpe_trades, sharpe_steps,
+           pnl_to_map_floor, fitness, final_cash;
+    int32_t trade_rows, fills_buy, fills_sell, final_inventory, steps, reserved;
+} sgmm_episode_summary;               /* 96 bytes */
+
+/* Summary of every episode of the batch, nothing written per step.  Exactly
+ * one of mm_genomes (TradingPolicy rows, as sgmm_rollout_trace: hidden in
+ * {8,16,32,64}, row stride mm_stride) and rules must be given; with rules,
+ * eps->genome[e] indexes rules, hidden / mm_stride are ignored and every
+ * rule's n_inventory must be eps->inv_max - eps->inv_min + 1 (rules is DEVICE
+ * memory: n_rules > 0 HOST copies may be passed in rules_host to have
+ * n_inventory, mode and quote_tick checked before the launch; NULL skips the
+ * check; with n_rules > 0 an episode whose genome[e] is outside [0, n_rules)
+ * is not walked and reports steps = 0).  No adversary (eps->adv is ignored): the reference's evaluation
+ * never runs one.  out: [eps->n].  One launch, no workspace. */
+int sgmm_rollout_summary(const sgmm_ticks *ticks, const sgmm_episodes *eps,
+                         const sgmm_env_params *params,
+                         const float *mm_genomes, int64_t mm_stride, int32_t hidden,
+                         const sgmm_quote_rule *rules, const sgmm_quote_rule *rules_host,
+                         int32_t n_rules, sgmm_episode_summary *out, void *stream);
+
+/* Per-step trace of rule episodes (main.py:99-132 run_benchmark_and_save,
+ * batched): sgmm_rollout_trace's outputs without the adversary / raw columns,
+ * indexed by step_off[e] + t; any may be NULL.  rules / rules_host / n_rules as
+ * sgmm_rollout_summary. */
+int sgmm_rule_trace(const sgmm_ticks *ticks, const sgmm_episodes *eps,
+                    const sgmm_env_params *params, const sgmm_quote_rule *rules,
+                    const sgmm_quote_rule *rules_host, int32_t n_rules,
+                    int32_t *off_a, int32_t *off_b, int32_t *inventory, double *cash,
+                    double *reward, double *pnl_reward, double *fee_paid,
+                    uint8_t *fill_buy, uint8_t *fill_sell,
+                    double *fitness, int32_t *trades, void *stream);
+
 /* NeuroEvolution.ask (models/model.py:65-71) on device:
  * out[i,k] = master[k] + z(seed, stream_id, gen, i0+i, k) * (float)sigma,
  * z ~ N(0,1) from Philox4x32-10 + Box-Muller (counter-based, so any rank can
