@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import AskedPopulation, GAHistory, GAState, check, ptr, stream_ptr
+from ._lib import GAHistory, GAState, check, ptr, stream_ptr
 from .model import NeuroEvolution, TradingPolicy, genome_size, genome_to_state_dict, hidden_from_genome
 from .rollout import EnvConfig, EpisodeBatch, RolloutEngine, TickStore, params_tensor
 from .shard import FitnessRecords, shard_bounds, shard_capacity  # noqa: F401 (re-exported)
@@ -210,22 +210,38 @@ class DRLEngine:
             print(msg)
             sys.stdout.flush()
 
+    @property
+    def device_path(self) -> bool:
+        """Populations generated inside the rollout kernels (MultiSession); else
+        the materialised-population TrainingSession."""
+        return self.rng == "device" and G_ok(self.hidden_dim)
+
     def session(self, train_bundle, val_bundle, train_stats, generations=100, output_prefix="agent"):
         """Device-resident training session: step(gen) enqueues one generation."""
+        if self.device_path:  # the K = 1 case of the populations path
+            return MultiSession([self], train_bundle, val_bundle, train_stats, generations, output_prefix,
+                                single=True)
         return TrainingSession(self, train_bundle, val_bundle, train_stats, generations, output_prefix)
 
     def train(self, train_bundle, val_bundle, train_stats, generations=100, output_prefix="agent"):
         sess = self.session(train_bundle, val_bundle, train_stats, generations, output_prefix)
-        for gen in range(0, generations, self.sync_every):
-            n = min(self.sync_every, generations - gen)
-            sess.steps(gen, n)
-            if n == self.sync_every:
-                sess.flush(gen + n)
-        return sess.finish()
+        return _run(sess, generations, self.sync_every)
 
 
-class _GraphedGenerations:
-    """Generation replay shared by TrainingSession and MultiSession.
+def _run(sess, generations, every):
+    """train(): steps, a flush after every full batch of ``every`` generations, finish."""
+    for gen in range(0, generations, every):
+        n = min(every, generations - gen)
+        sess.steps(gen, n)
+        if n == every:
+            sess.flush(gen + n)
+    return sess.finish()
+
+
+class _Session:
+    """What MultiSession and TrainingSession share: the device state of the K
+    populations (K = 1 in TrainingSession), generation replay, and the host
+    side of the history rows (log lines, checkpoints, the evolvers' state).
 
     A generation is _rollout, _exchange, _boundary (the last two no-ops on one
     unsharded process).  With use_graph it is captured once and replayed; when
@@ -234,10 +250,65 @@ class _GraphedGenerations:
     GRAPH_BATCH generations are captured into one graph as well, so several
     ranks also run one host launch per batch.  Otherwise (gloo: the gather is
     staged through host memory) the rollout and the GA step are two graphs
-    around an eager all-gather."""
+    around an eager all-gather.
+
+    Nothing in step() waits for the device; flush() brings history rows to the
+    host, prints the reference's log lines in order and writes the checkpoints."""
 
     # generations per captured multi-generation graph
     GRAPH_BATCH = 16
+
+    def _setup(self, engs, generations, output_prefix, single):
+        """engs: the K engines (same pop_size, hidden_dim, use_arl); single: the
+        DRLEngine.train form -- bare log lines, finish() returns one result."""
+        _lib.require_gpu()
+        self.engs, self.single = engs, single
+        e0 = engs[0]
+        K = self.K = len(engs)
+        # a session owns its workspace: a captured graph keeps raw pointers to it
+        self.roll = RolloutEngine(e0.device or "cuda")
+        dev = self.dev = self.roll.device
+        self.L = self.roll.L
+        self.group, self.rank, self.world, self.group_active = _dist_info(e0.dist)
+        self.sharded = self.world > 1 or e0.exchange == "always"
+        P, H = self.P, self.H = e0.pop_size, e0.hidden_dim
+        G = self.G = genome_size(H)
+        self.i0, self.i1 = shard_bounds(P, self.rank, self.world)
+        self.n_loc = self.i1 - self.i0
+        self.n_cap = shard_capacity(P, self.world)  # record slots per rank and population
+        arl = self.arl = e0.use_arl
+        self.generations = int(generations)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.masters = torch.stack([e.mm_evolver.master_policy.get_weights() for e in engs]).to(**f32).contiguous()
+        self.masters_adv = torch.stack([e.adv_evolver.master_policy.get_weights() for e in engs]).to(**f32) \
+            .contiguous() if arl else None
+        self.best_masters = torch.zeros((K, G), **f32)
+        self.states = torch.zeros((K, HIST_STATE_SIZES[0]), dtype=torch.uint8, device=dev)
+        self.hist = torch.zeros((K, self.generations, HIST_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        for k, e in enumerate(engs):
+            if arl and e.adv_evolver.sigma != e.mm_evolver.sigma:
+                raise ValueError("mm and adversary sigma must start equal (one device state holds both)")
+            check(self.L.sgmm_ga_state_init(ptr(self.states[k]), float(e.mm_evolver.sigma), e.patience, e.decay,
+                                            stream_ptr()), "sgmm_ga_state_init")
+        # one generation = fixed launches -> replayable HIP graphs
+        self.use_graph = bool(e0.use_graph)
+        self.graphs, self.batch_graph, self.batch_graphs, self.full_graph = None, None, {}, False
+        self.graph_batch = max(1, min(self.GRAPH_BATCH, e0.sync_every))
+        self.best_paths = [os.path.join(e.save_dir, f"{output_prefix}_best_val_{e.phi}.pth") for e in engs]
+        self.saved_any = [False] * K
+        self.emitted = 0
+        self.history = [{"gen": [], "train_f": [], "val_f": [], "train_trades": [], "val_trades": []}
+                        for _ in range(K)]
+        self.ev0 = torch.cuda.Event(enable_timing=True)  # DRLEngine.timing: recorded when __init__ ends
+        self.ev1 = torch.cuda.Event(enable_timing=True)
+
+    def _slots(self, off, T):
+        """One phase's episode slots of a population, in record order: n_cap of
+        them, the shard's n_loc individuals first, then zero-length pads (never
+        read back).  Returns (genome, tick_off, length)."""
+        n, n_loc = self.n_cap, self.n_loc
+        pad = np.zeros(n - n_loc, np.int64)
+        return np.concatenate([np.arange(n_loc), pad]), np.full(n, off), np.concatenate([np.full(n_loc, T), pad])
 
     def _gen(self):
         self._rollout()
@@ -321,57 +392,103 @@ class _GraphedGenerations:
         for g in range(gen0 + done, gen0 + n):
             self.step(g)
 
+    def _exchange(self):
+        """The generation's one collective: all-gather the per-rank records."""
+        if self.sharded:
+            self.rec.all_gather(self.group)
 
-class TrainingSession(_GraphedGenerations):
-    """One DRLEngine.train run, resident on the GPU (drl_engine.py:83-178).
+    def _emit(self, k: int, rows, g0: int):
+        """Population k's history rows g0, g0 + 1, ...: history entries, the
+        reference's log lines (drl_engine.py:147-171; prefixed with the
+        population's phi unless single) and the checkpoint when any improved."""
+        e, h = self.engs[k], self.history[k]
+        pre = "" if self.single else f"[phi={e.phi}] "
+        tag = "ARL:ON" if self.arl else "ARL:OFF"
+        improved_any = False
+        for g, r in enumerate(rows, g0):
+            imp = bool(r["flags"] & 1)
+            improved_any |= imp
+            if r["flags"] & 2:
+                e._log(f"{pre}>>> Sigma decayed to {r['sigma_after']:.4f} due to no improvement")
+            h["gen"].append(g)
+            h["train_f"].append(np.float64(r["train_f"]))
+            h["val_f"].append(np.float64(r["val_f"]))
+            h["train_trades"].append(int(r["train_trades"]))
+            h["val_trades"].append(int(r["val_trades"]))
+            if g % 5 == 0:
+                e._log(f"{pre}Gen {g:03d} | {tag} | Best Train: {r['train_f']:.2f} | "
+                       f"Val: {r['val_f']:.2f}{'*' if imp else ''}")
+        if improved_any and self.rank == 0:
+            torch.save(genome_to_state_dict(self.best_masters[k], self.H), self.best_paths[k])
+        self.saved_any[k] |= improved_any
+
+    def flush(self, upto: int):
+        """History rows [emitted, upto) of every population to the host."""
+        if upto <= self.emitted:
+            return
+        rows_all = self.hist[:, self.emitted:upto].cpu().numpy()
+        for k in range(self.K):
+            self._emit(k, rows_all[k].reshape(-1).view(HIST_DTYPE), self.emitted)
+        self.emitted = upto
+
+    def _copy_back(self, k: int, st, ms: float):
+        """Population k's sigma and masters back into its engine's evolvers, the
+        best-validation weights reloaded (drl_engine.py:174-178)."""
+        e = self.engs[k]
+        e.mm_evolver.sigma = float(st["sigma_mm"])
+        e.mm_evolver.master_policy.set_weights(self.masters[k].cpu())
+        if self.arl:
+            e.adv_evolver.sigma = float(st["sigma_adv"])
+            e.adv_evolver.master_policy.set_weights(self.masters_adv[k].cpu())
+        if self.saved_any[k]:
+            e.mm_evolver.master_policy.load_state_dict(genome_to_state_dict(self.best_masters[k], self.H))
+        elif os.path.exists(self.best_paths[k]):
+            e.mm_evolver.master_policy.load_state_dict(torch.load(self.best_paths[k], weights_only=True))
+        e.timing = {"generations": self.generations, "ms": ms,
+                    "env_steps": self.generations * self.P * self.T_tr[k]}
+        return e.mm_evolver.master_policy, self.history[k]
+
+    def finish(self):
+        """Flush and copy the evolver state back; returns the K
+        (master_policy, history) results in engine order, or the one when single."""
+        self.ev1.record()
+        self.flush(self.generations)
+        torch.cuda.synchronize()
+        ms = self.ev0.elapsed_time(self.ev1)  # the session's life on the stream, shared by its engines
+        st = self.states.cpu().numpy().reshape(-1).view(STATE_DTYPE)
+        out = [self._copy_back(k, st[k], ms) for k in range(self.K)]
+        return out[0] if self.single else out
+
+
+class TrainingSession(_Session):
+    """One DRLEngine.train run (drl_engine.py:83-178) with the population
+    materialised in device memory: rng="torch" (the host draws it from the
+    reference's generator) and rng="device" with a genome too large for the
+    in-kernel ask and GA step (not G_ok: hidden_dim=64).
 
     Per generation (step): ask the shard's genomes -> roll the shard out (train,
     plus validation when fused) -> all-gather fitness over ranks -> tell both
-    evolvers -> validation bookkeeping (checkpoint slot, sigma decay, history).
-    Nothing in step() waits for the device; flush() brings history rows to the
-    host, prints the reference's log lines in order and writes the checkpoint."""
+    evolvers -> validation bookkeeping (checkpoint slot, sigma decay, history)."""
 
     def __init__(self, eng: DRLEngine, train_bundle, val_bundle, train_stats, generations, output_prefix):
-        _lib.require_gpu()
+        self._setup([eng], generations, output_prefix, single=True)
         self.e = eng
-        # a session owns its workspace: a captured graph keeps raw pointers to it
-        self.roll = RolloutEngine(eng.device or "cuda")
-        dev = self.dev = self.roll.device
-        self.L = self.roll.L
-        self.group, self.rank, self.world, self.group_active = _dist_info(eng.dist)
-        self.sharded = self.world > 1 or eng.exchange == "always"
-        P, H = eng.pop_size, eng.hidden_dim
-        self.P, self.H, self.G = P, H, genome_size(H)
-        G = self.G
-        self.i0, self.i1 = shard_bounds(P, self.rank, self.world)
-        n_loc = self.n_loc = self.i1 - self.i0
-        n_cap = self.n_cap = shard_capacity(P, self.world)  # record slots per rank
-        arl = self.arl = eng.use_arl
+        dev, P, G, arl, n_cap = self.dev, self.P, self.G, self.arl, self.n_cap
+        self.master, self.best_master, self.state = self.masters[0], self.best_masters[0], self.states[0]
+        self.master_adv = self.masters_adv[0] if arl else None
         self.fused = not _best_validation(eng.val_mode, n_cap)
         self.torch_rng = eng.rng == "torch"
-        # device RNG, validation of the best: the populations path with K = 1
-        # (asked rollout + tell in its tail, then the new master's validation)
-        self.best_step = not self.torch_rng and not self.fused and G_ok(H)
-        self.generations = int(generations)
         # (rng="torch" with world > 1: every rank draws the identical full
         # population from its identically seeded generator)
         self.ticks = device_ticks([train_bundle, val_bundle], train_stats, dev)
-        (tr_off, self.T_tr), (va_off, self.T_va) = self.ticks.segments
+        (tr_off, T_tr), (va_off, self.T_va) = self.ticks.segments
+        self.T_tr = [T_tr]
         self.params = params_tensor([EnvConfig(phi=eng.phi, tick_size=eng.tick_size,
                                                fee_rate=eng.fee_rate)], dev)
-        # episode slots follow the record layout: n_cap per phase, the shard's
-        # n_loc individuals first, then zero-length pads (never read back)
-        pad = n_cap - n_loc
-
-        def phase(off, T):
-            return (np.concatenate([np.arange(n_loc), np.zeros(pad, np.int64)]),
-                    np.full(n_cap, off), np.concatenate([np.full(n_loc, T), np.zeros(pad, np.int64)]))
-
-        g_tr, o_tr, l_tr = phase(tr_off, self.T_tr)
-        g_va, o_va, l_va = phase(va_off, self.T_va)
-        self.rec = FitnessRecords(P, self.world, dev, gather=self.sharded, with_val=not self.best_step,
-                                  group_active=self.group_active)
+        g_tr, o_tr, l_tr = self._slots(tr_off, T_tr)
+        self.rec = FitnessRecords(P, self.world, dev, gather=self.sharded, group_active=self.group_active)
         if self.fused:  # one launch: training + validation episodes of the shard
+            g_va, o_va, l_va = self._slots(va_off, self.T_va)
             adv = np.concatenate([g_tr, np.full(n_cap, -1)]) if arl else None  # validation: no adversary
             self.train_eps = EpisodeBatch(np.concatenate([g_tr, g_va]), np.concatenate([o_tr, o_va]),
                                           np.concatenate([l_tr, l_va]), np.zeros(2 * n_cap), adv=adv).to(dev)
@@ -390,140 +507,41 @@ class TrainingSession(_GraphedGenerations):
         # population rows: the full population when the host draws it (torch
         # RNG), else the shard's capacity (pads point at row 0, which exists)
         n_rows = P if self.torch_rng else max(n_cap, 1)
-        if not self.torch_rng and G <= 4096:
-            n_rows = 1  # asked population: generated inside the rollout (placeholder row)
         self.pop = torch.empty((n_rows, G), **f32)
         lo = min(self.i0, P - 1)
         self.pop_loc = self.pop[lo:lo + max(n_cap, 1)] if self.torch_rng else self.pop
         self.adv_pop = torch.empty((n_rows, ADV_GENOME), **f32) if arl else None
         self.adv_loc = (self.adv_pop[lo:lo + max(n_cap, 1)] if self.torch_rng else self.adv_pop) if arl else None
-        self.master = eng.mm_evolver.master_policy.get_weights().to(**f32)
-        self.master_adv = eng.adv_evolver.master_policy.get_weights().to(**f32) if arl else None
-        self.best_master = torch.zeros(G, **f32)
-        self.state = torch.zeros(HIST_STATE_SIZES[0], dtype=torch.uint8, device=dev)
-        self.hist = torch.zeros((self.generations, HIST_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-        if arl and eng.adv_evolver.sigma != eng.mm_evolver.sigma:
-            raise ValueError("mm and adversary sigma must start equal (one device state holds both)")
-        check(self.L.sgmm_ga_state_init(ptr(self.state), float(eng.mm_evolver.sigma), eng.patience,
-                                        eng.decay, stream_ptr()), "sgmm_ga_state_init")
-        # device RNG + fused validation: the population is never materialized --
-        # the rollout kernels generate each individual's genome from the master
-        # and the GA state, and the GA step runs in the rollout's last workgroup
-        # (one process) or after the all-gather (several ranks)
-        self.fast_step = (not self.torch_rng and self.fused and G <= 4096 and ADV_GENOME <= 4096)
-        self.asked = AskedPopulation(self.state.data_ptr(), self.master.data_ptr(),
-                                     self.master_adv.data_ptr() if arl else None, eng.seed, self.i0, 0)
-        self.seeds = torch.tensor([int(eng.seed)], dtype=torch.int64).to(dev)
-        # the frontier kernel's walk order, rewritten on the device by the walk-order
-        # feedback (sgmm_populations::walk_order); train_eps stays read-only
-        self.walk_order = self.train_eps.dev["order"].clone()
-        self.pops = _lib.Populations(1, P, H, self.generations, self.state.data_ptr(), self.master.data_ptr(),
-                                     self.master_adv.data_ptr() if arl else None, self.best_master.data_ptr(),
-                                     self.seeds.data_ptr(), self.hist.data_ptr(),
-                                     self.walk_order.data_ptr() if eng.walk_feedback else None)
-        # one generation = fixed launches -> replayable HIP graphs: the whole
-        # generation on one rank; with several ranks the rollout and the boundary
-        # are captured separately around the (eager) all-gather
-        self.use_graph = bool(eng.use_graph) and not self.torch_rng
-        self.graphs, self.batch_graph, self.batch_graphs, self.full_graph = None, None, {}, False
-        self.graph_batch = max(1, min(self.GRAPH_BATCH, eng.sync_every))
+        # the host draw waits for the device's sigma every generation: no graph
+        self.use_graph = self.use_graph and not self.torch_rng
         self.roll.reserve(self.train_eps, arl)
         if self.val_eps is not None:
             self.roll.reserve(self.val_eps, False)
-        self.best_path = os.path.join(eng.save_dir, f"{output_prefix}_best_val_{eng.phi}.pth")
-        self.saved_any = False
-        self.emitted = 0
-        self.history = {"gen": [], "train_f": [], "val_f": [], "train_trades": [], "val_trades": []}
-        self.ev0 = torch.cuda.Event(enable_timing=True)
-        self.ev1 = torch.cuda.Event(enable_timing=True)
         self.ev0.record()
 
-    def _ask(self):
-        """ask() of the shard (models/model.py:65-71) from the device master/sigma."""
-        e, L, s, G = self.e, self.L, stream_ptr(), self.G
-        check(L.sgmm_ga_ask(ptr(self.master), G, ptr(self.state), 0, e.seed, self.i0, self.n_loc,
-                            ptr(self.pop), G, s), "sgmm_ga_ask")
-        if self.arl:
-            check(L.sgmm_ga_ask(ptr(self.master_adv), ADV_GENOME, ptr(self.state), 1, e.seed, self.i0,
-                                self.n_loc, ptr(self.adv_pop), ADV_GENOME, s), "sgmm_ga_ask(adv)")
-
     def _rollout(self):
-        """ask (host draw / device kernel / generated in-kernel) + the shard's
-        rollouts (drl_engine.py:104-115, plus the fused validation episodes);
-        with one process and the asked population the whole generation,
-        including the GA step, is this one call."""
-        P = self.P
-        L, s = self.L, stream_ptr()
-        if self.best_step:
-            tk, ep = self.ticks.struct(), self.train_eps.struct()
-            ws = self.roll.workspace(self.train_eps, self.arl)
-            f, t = self.out
-            if not self.sharded:
-                vep = self.val_eps.struct()
-                vf, vt = self.vout
-                check(L.sgmm_generation_multi_best(ctypes.byref(tk), ctypes.byref(ep), ctypes.byref(vep),
-                                                   ptr(self.params), ctypes.byref(self.pops), ptr(f), ptr(t),
-                                                   ptr(vf), ptr(vt), ptr(ws), ws.numel(), s),
-                      "sgmm_generation_multi_best")
-            else:
-                check(L.sgmm_rollout_fitness_asked(ctypes.byref(tk), ctypes.byref(ep), ptr(self.params),
-                                                   ctypes.byref(self.asked), self.H, ptr(f), ptr(t), ptr(ws),
-                                                   ws.numel(), s), "sgmm_rollout_fitness_asked")
-            return
-        if self.fast_step:
-            tk, ep = self.ticks.struct(), self.train_eps.struct()
-            ws = self.roll.workspace(self.train_eps, self.arl)
-            f, t = self.out
-            if not self.sharded:
-                check(L.sgmm_generation(ctypes.byref(tk), ctypes.byref(ep), ptr(self.params), ptr(self.state),
-                                        ptr(self.master), ptr(self.master_adv) if self.arl else None,
-                                        ptr(self.best_master), self.H, self.e.seed, P, ptr(f), ptr(t),
-                                        ptr(self.hist), self.generations, ptr(ws), ws.numel(), s),
-                      "sgmm_generation")
-            else:
-                check(L.sgmm_rollout_fitness_asked(ctypes.byref(tk), ctypes.byref(ep), ptr(self.params),
-                                                   ctypes.byref(self.asked), self.H, ptr(f), ptr(t), ptr(ws),
-                                                   ws.numel(), s), "sgmm_rollout_fitness_asked")
-            return
+        """ask (host draw / device kernel) + the shard's rollouts
+        (drl_engine.py:104-115, plus the fused validation episodes)."""
+        e, L, s, G, P = self.e, self.L, stream_ptr(), self.G, self.P
         if self.torch_rng:
             st_now = self.state.cpu().numpy().view(STATE_DTYPE)[0]
             self.pop.copy_(_host_ask(self.master, float(st_now["sigma_mm"]), P))
             if self.arl:
                 self.adv_pop.copy_(_host_ask(self.master_adv, float(st_now["sigma_adv"]), P))
-        else:
-            self._ask()
+        else:  # ask() of the shard (models/model.py:65-71) from the device master/sigma
+            check(L.sgmm_ga_ask(ptr(self.master), G, ptr(self.state), 0, e.seed, self.i0, self.n_loc,
+                                ptr(self.pop), G, s), "sgmm_ga_ask")
+            if self.arl:
+                check(L.sgmm_ga_ask(ptr(self.master_adv), ADV_GENOME, ptr(self.state), 1, e.seed, self.i0,
+                                    self.n_loc, ptr(self.adv_pop), ADV_GENOME, s), "sgmm_ga_ask(adv)")
         self.roll.fitness(self.ticks, self.train_eps, self.params, self.pop_loc, self.H, self.adv_loc,
                           out=self.out)
 
-    def _exchange(self):
-        """The generation's one collective: all-gather the per-rank records."""
-        if self.sharded:
-            self.rec.all_gather(self.group)
-
     def _boundary(self):
-        """tell both evolvers, validation bookkeeping, sigma decay (after the
-        exchange; a no-op when the generation call already did it)."""
+        """tell both evolvers, validation bookkeeping, sigma decay (after the exchange)."""
         e, L, s = self.e, self.L, stream_ptr()
         P, G = self.P, self.G
         arl = self.arl
-        if self.best_step:
-            if self.sharded:  # every rank: tell on the gathered records, then validate the new master
-                check(L.sgmm_ga_tell_multi(ctypes.byref(self.pops), *self.rec.tell_args(), s), "sgmm_ga_tell_multi")
-                tk, vep = self.ticks.struct(), self.val_eps.struct()
-                ws = self.roll.workspace(self.val_eps, False)
-                vf, vt = self.vout
-                check(L.sgmm_validate_multi(ctypes.byref(tk), ctypes.byref(vep), ptr(self.params),
-                                            ctypes.byref(self.pops), ptr(vf), ptr(vt), ptr(ws), ws.numel(), s),
-                      "sgmm_validate_multi")
-            return
-        if self.fast_step:
-            if self.sharded:
-                check(L.sgmm_ga_step(ptr(self.state), *self.rec.step_args(),
-                                     ptr(self.master), ptr(self.master_adv) if arl else None,
-                                     ptr(self.best_master), G, ADV_GENOME if arl else 0, e.seed,
-                                     ptr(self.hist), self.generations, None, None, 0, 0, s),
-                      "sgmm_ga_step")
-            return
         tr_f, tr_t, va_f, va_t = self.rec.population()
         # tell both evolvers (model.py:73-76, drl_engine.py:119-125)
         check(L.sgmm_ga_tell(ptr(self.state), ptr(tr_f), ptr(tr_t), P, ptr(self.master),
@@ -542,54 +560,6 @@ class TrainingSession(_GraphedGenerations):
                                    self.generations, s), "sgmm_ga_val_update")
         if self.torch_rng:
             TradingPolicy()  # the reference's validation builds a TradingPolicy() (RNG draw)
-
-    def flush(self, upto: int):
-        """History rows [emitted, upto) to the host: log lines, checkpoint."""
-        if upto <= self.emitted:
-            return
-        e = self.e
-        rows = self.hist[self.emitted:upto].cpu().numpy().view(HIST_DTYPE).reshape(-1)
-        improved_any = False
-        for k, r in enumerate(rows):
-            g = self.emitted + k
-            imp = bool(r["flags"] & 1)
-            improved_any |= imp
-            if r["flags"] & 2:
-                e._log(f">>> Sigma decayed to {r['sigma_after']:.4f} due to no improvement")
-            self.history["gen"].append(g)
-            self.history["train_f"].append(np.float64(r["train_f"]))
-            self.history["val_f"].append(np.float64(r["val_f"]))
-            self.history["train_trades"].append(int(r["train_trades"]))
-            self.history["val_trades"].append(int(r["val_trades"]))
-            if g % 5 == 0:
-                tag = "ARL:ON" if self.arl else "ARL:OFF"
-                e._log(f"Gen {g:03d} | {tag} | Best Train: {r['train_f']:.2f} | "
-                       f"Val: {r['val_f']:.2f}{'*' if imp else ''}")
-        if improved_any and self.rank == 0:
-            torch.save(genome_to_state_dict(self.best_master, self.H), self.best_path)
-        self.saved_any |= improved_any
-        self.emitted = upto
-
-    def finish(self):
-        """Flush, copy the evolver state back, reload the best-validation weights
-        (drl_engine.py:174-178); returns (master_policy, history)."""
-        e = self.e
-        self.ev1.record()
-        self.flush(self.generations)
-        torch.cuda.synchronize()
-        e.timing = {"generations": self.generations, "ms": self.ev0.elapsed_time(self.ev1),
-                    "env_steps": self.generations * self.P * self.T_tr}
-        st = self.state.cpu().numpy().view(STATE_DTYPE)[0]
-        e.mm_evolver.sigma = float(st["sigma_mm"])
-        e.mm_evolver.master_policy.set_weights(self.master.cpu())
-        if self.arl:
-            e.adv_evolver.sigma = float(st["sigma_adv"])
-            e.adv_evolver.master_policy.set_weights(self.master_adv.cpu())
-        if self.saved_any:
-            e.mm_evolver.master_policy.load_state_dict(genome_to_state_dict(self.best_master, self.H))
-        elif os.path.exists(self.best_path):
-            e.mm_evolver.master_policy.load_state_dict(torch.load(self.best_path, weights_only=True))
-        return e.mm_evolver.master_policy, self.history
 
 
 class MultiDRLEngine:
@@ -632,11 +602,10 @@ class MultiDRLEngine:
     @property
     def fused_path(self) -> bool:
         """All populations on the shared device path (else: one after another)."""
-        return all(e.rng == "device" and genome_size(e.hidden_dim) <= 4096 for e in self.engines) and \
-            len({e.val_mode for e in self.engines}) == 1
+        return all(e.device_path for e in self.engines) and len({e.val_mode for e in self.engines}) == 1
 
     def session(self, train_bundles, val_bundles, train_stats, generations=100, output_prefix="agent"):
-        return MultiSession(self, train_bundles, val_bundles, train_stats, generations, output_prefix)
+        return MultiSession(self.engines, train_bundles, val_bundles, train_stats, generations, output_prefix)
 
     def train(self, train_bundles, val_bundles, train_stats, generations=100, output_prefix="agent"):
         K = len(self.engines)
@@ -644,13 +613,7 @@ class MultiDRLEngine:
         if not self.fused_path:  # reference order: one DRLEngine.train after another
             return [e.train(tr[k], va[k], st[k], generations, output_prefix) for k, e in enumerate(self.engines)]
         sess = self.session(tr, va, st, generations, output_prefix)
-        every = self.engines[0].sync_every
-        for gen in range(0, generations, every):
-            n = min(every, generations - gen)
-            sess.steps(gen, n)
-            if n == every:
-                sess.flush(gen + n)
-        return sess.finish()
+        return _run(sess, generations, self.engines[0].sync_every)
 
 
 def _per_pop(x, K):
@@ -663,31 +626,21 @@ def _per_pop(x, K):
     return x
 
 
-class MultiSession(_GraphedGenerations):
-    """K DRLEngine.train runs resident on the GPU, one launch pair per
-    generation for all of them (sgmm_generation_multi), or -- with several
-    ranks -- the asked rollout of every population's shard, one all-gather of
-    the K records and one K-workgroup GA step (sgmm_ga_step_multi)."""
+class MultiSession(_Session):
+    """K DRLEngine.train runs (K >= 1; DRLEngine.train itself is K = 1, single)
+    resident on the GPU, genomes generated inside the rollout kernels from each
+    population's master, sigma and Philox key, one launch pair per generation
+    for all of them (sgmm_generation_multi; validation of the best:
+    sgmm_generation_multi_best), or -- sharded -- the asked rollout of every
+    population's shard (sgmm_rollout_fitness_asked_multi), one all-gather of the
+    K records and one K-workgroup GA step (sgmm_ga_step_multi; validation of the
+    best: sgmm_ga_tell_multi, then sgmm_validate_multi)."""
 
-    def __init__(self, meng: MultiDRLEngine, train_bundles, val_bundles, train_stats, generations,
-                 output_prefix):
-        _lib.require_gpu()
-        engs = self.engs = meng.engines
-        e0 = engs[0]
-        K = self.K = len(engs)
+    def __init__(self, engs, train_bundles, val_bundles, train_stats, generations, output_prefix, single=False):
+        self._setup(list(engs), generations, output_prefix, single)
+        engs, e0, K = self.engs, self.engs[0], self.K
+        dev, P, H, arl, n = self.dev, self.P, self.H, self.arl, self.n_cap
         tr, va, sts = (_per_pop(x, K) for x in (train_bundles, val_bundles, train_stats))
-        self.roll = RolloutEngine(e0.device or "cuda")
-        dev = self.dev = self.roll.device
-        self.L = self.roll.L
-        self.group, self.rank, self.world, self.group_active = _dist_info(e0.dist)
-        self.sharded = self.world > 1 or e0.exchange == "always"
-        P, H = self.P, self.H = e0.pop_size, e0.hidden_dim
-        G = self.G = genome_size(H)
-        self.i0, self.i1 = shard_bounds(P, self.rank, self.world)
-        n_loc = self.n_loc = self.i1 - self.i0
-        n = self.n_cap = shard_capacity(P, self.world)
-        arl = self.arl = e0.use_arl
-        self.generations = int(generations)
         # tick columns: each distinct (bundle, stats) once
         self.ticks = TickStore()
         seg_of = {}
@@ -708,19 +661,18 @@ class MultiSession(_GraphedGenerations):
         # population's new master after the tell (the reference's order:
         # sgmm_generation_multi_best, four launches but K validation episodes
         # instead of K * P)
-        self.best_val = _best_validation(e0.val_mode, n, K)
-        # episodes: per population n training slots (then n validation slots
-        # when fused) -- the shard's n_loc individuals first, zero-length pads after
-        pad = n - n_loc
+        self.best_val = _best_validation(e0.val_mode, n)
+        # episodes: per population n training slots (then n validation slots when fused)
         g, off, ln, par, adv = [], [], [], [], []
         for k, ((to, T), (vo, Tv)) in enumerate(segs):
             phases = ((to, T, True),) if self.best_val else ((to, T, True), (vo, Tv, False))
             for o, L_, is_tr in phases:
-                g.append(np.concatenate([np.arange(n_loc), np.zeros(pad, np.int64)]))
-                off.append(np.full(n, o))
-                ln.append(np.concatenate([np.full(n_loc, L_), np.zeros(pad, np.int64)]))
+                gk, ok, lk = self._slots(o, L_)
+                g.append(gk)
+                off.append(ok)
+                ln.append(lk)
                 par.append(np.full(n, k))
-                adv.append(g[-1] if is_tr else np.full(n, -1))  # validation: no adversary
+                adv.append(gk if is_tr else np.full(n, -1))  # validation: no adversary
         self.eps = EpisodeBatch(np.concatenate(g), np.concatenate(off), np.concatenate(ln), np.concatenate(par),
                                 adv=np.concatenate(adv) if arl else None).to(dev)
         # best: one validation episode per population, genome row k = master k
@@ -731,19 +683,7 @@ class MultiSession(_GraphedGenerations):
                      torch.zeros(K, dtype=torch.int32, device=dev)) if self.best_val else None
         self.rec = FitnessRecords(P, self.world, dev, n_pop=K, gather=self.sharded, with_val=not self.best_val,
                                   group_active=self.group_active)
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.masters = torch.stack([e.mm_evolver.master_policy.get_weights() for e in engs]).to(**f32).contiguous()
-        self.masters_adv = torch.stack([e.adv_evolver.master_policy.get_weights() for e in engs]).to(**f32) \
-            .contiguous() if arl else None
-        self.best_masters = torch.zeros((K, G), **f32)
-        self.states = torch.zeros((K, HIST_STATE_SIZES[0]), dtype=torch.uint8, device=dev)
-        self.hist = torch.zeros((K, self.generations, HIST_DTYPE.itemsize), dtype=torch.uint8, device=dev)
         self.seeds = torch.tensor([int(e.seed) for e in engs], dtype=torch.int64).to(dev)
-        for k, e in enumerate(engs):
-            if arl and e.adv_evolver.sigma != e.mm_evolver.sigma:
-                raise ValueError("mm and adversary sigma must start equal (one device state holds both)")
-            check(self.L.sgmm_ga_state_init(ctypes.c_void_p(self.states[k].data_ptr()), float(e.mm_evolver.sigma),
-                                            e.patience, e.decay, stream_ptr()), "sgmm_ga_state_init")
         # the frontier kernel's walk order, rewritten on the device by the walk-order
         # feedback (sgmm_populations::walk_order); the episode batch stays read-only
         self.walk_order = self.eps.dev["order"].clone()
@@ -751,17 +691,10 @@ class MultiSession(_GraphedGenerations):
                                      self.masters_adv.data_ptr() if arl else None, self.best_masters.data_ptr(),
                                      self.seeds.data_ptr(), self.hist.data_ptr(),
                                      self.walk_order.data_ptr() if e0.walk_feedback else None)
-        self.use_graph = bool(e0.use_graph)
-        self.graphs, self.batch_graph, self.batch_graphs, self.full_graph = None, None, {}, False
-        self.graph_batch = max(1, min(self.GRAPH_BATCH, e0.sync_every))
         self.roll.reserve(self.eps, arl)
         if self.val_eps is not None:
             self.roll.reserve(self.val_eps, False)
-        self.best_paths = [os.path.join(e.save_dir, f"{output_prefix}_best_val_{e.phi}.pth") for e in engs]
-        self.saved_any = [False] * K
-        self.emitted = 0
-        self.history = [{"gen": [], "train_f": [], "val_f": [], "train_trades": [], "val_trades": []}
-                        for _ in range(K)]
+        self.ev0.record()
 
     # one generation: rollout (+ GA step in its tail on one process)
     def _rollout(self):
@@ -786,10 +719,6 @@ class MultiSession(_GraphedGenerations):
                                                           ptr(f), ptr(t), ptr(ws), ws.numel(), stream_ptr()),
                   "sgmm_rollout_fitness_asked_multi")
 
-    def _exchange(self):
-        if self.sharded:
-            self.rec.all_gather(self.group)
-
     def _boundary(self):
         if not self.sharded:
             return
@@ -806,55 +735,6 @@ class MultiSession(_GraphedGenerations):
             check(self.L.sgmm_ga_step_multi(ctypes.byref(self.pops), *self.rec.multi_step_args(), stream_ptr()),
                   "sgmm_ga_step_multi")
 
-    def flush(self, upto: int):
-        """History rows [emitted, upto) of every population: the reference's log
-        lines (prefixed with the population's phi), checkpoints."""
-        if upto <= self.emitted:
-            return
-        rows_all = self.hist[:, self.emitted:upto].cpu().numpy()
-        for k, e in enumerate(self.engs):
-            rows = rows_all[k].reshape(-1).view(HIST_DTYPE)
-            improved_any = False
-            h = self.history[k]
-            for j, r in enumerate(rows):
-                g = self.emitted + j
-                imp = bool(r["flags"] & 1)
-                improved_any |= imp
-                if r["flags"] & 2:
-                    e._log(f"[phi={e.phi}] >>> Sigma decayed to {r['sigma_after']:.4f} due to no improvement")
-                h["gen"].append(g)
-                h["train_f"].append(np.float64(r["train_f"]))
-                h["val_f"].append(np.float64(r["val_f"]))
-                h["train_trades"].append(int(r["train_trades"]))
-                h["val_trades"].append(int(r["val_trades"]))
-                if g % 5 == 0:
-                    tag = "ARL:ON" if self.arl else "ARL:OFF"
-                    e._log(f"[phi={e.phi}] Gen {g:03d} | {tag} | Best Train: {r['train_f']:.2f} | "
-                           f"Val: {r['val_f']:.2f}{'*' if imp else ''}")
-            if improved_any and self.rank == 0:
-                torch.save(genome_to_state_dict(self.best_masters[k], self.H), self.best_paths[k])
-            self.saved_any[k] |= improved_any
-        self.emitted = upto
-
-    def finish(self):
-        self.flush(self.generations)
-        torch.cuda.synchronize()
-        st = self.states.cpu().numpy().reshape(-1).view(STATE_DTYPE)
-        out = []
-        for k, e in enumerate(self.engs):
-            e.mm_evolver.sigma = float(st[k]["sigma_mm"])
-            e.mm_evolver.master_policy.set_weights(self.masters[k].cpu())
-            if self.arl:
-                e.adv_evolver.sigma = float(st[k]["sigma_adv"])
-                e.adv_evolver.master_policy.set_weights(self.masters_adv[k].cpu())
-            if self.saved_any[k]:
-                e.mm_evolver.master_policy.load_state_dict(genome_to_state_dict(self.best_masters[k], self.H))
-            elif os.path.exists(self.best_paths[k]):
-                e.mm_evolver.master_policy.load_state_dict(torch.load(self.best_paths[k], weights_only=True))
-            e.timing = {"generations": self.generations}
-            out.append((e.mm_evolver.master_policy, self.history[k]))
-        return out
-
 
 # ---------------------------------------------------------------------- small helpers
 # val_mode="auto": validate only the best (after the tell) from this many
@@ -868,20 +748,10 @@ def G_ok(hidden: int) -> bool:
     return genome_size(hidden) <= 4096 and ADV_GENOME <= 4096
 
 
-def _best_validation(val_mode: str, n_shard: int, n_pop: int = 1) -> bool:
+def _best_validation(val_mode: str, n_shard: int) -> bool:
     if val_mode not in ("auto", "fused", "best"):
         raise ValueError("val_mode must be 'auto', 'fused' or 'best'")
     return val_mode == "best" or (val_mode == "auto" and n_shard >= BEST_VAL_MIN_SHARD)
-
-
-def ctypes_size(t):
-    import ctypes
-    return ctypes.sizeof(t)
-
-
-def ctypes_offset_ptr(tensor, offset):
-    import ctypes
-    return ctypes.c_void_p(tensor.data_ptr() + int(offset))
 
 
 HIST_DTYPE = np.dtype([("train_f", "<f8"), ("val_f", "<f8"), ("sigma_after", "<f8"),
@@ -892,7 +762,7 @@ STATE_DTYPE = np.dtype([("sigma_mm", "<f8"), ("sigma_adv", "<f8"), ("best_val", 
                         ("best_idx", "<i4"), ("adv_best_idx", "<i4"), ("gen", "<i4"),
                         ("improved", "<i4"), ("decayed", "<i4"), ("patience", "<i4"),
                         ("arrivals", "<i4"), ("decay", "<f8")])
-assert HIST_DTYPE.itemsize == ctypes_size(GAHistory) and STATE_DTYPE.itemsize == ctypes_size(GAState)
+assert HIST_DTYPE.itemsize == ctypes.sizeof(GAHistory) and STATE_DTYPE.itemsize == ctypes.sizeof(GAState)
 HIST_STATE_SIZES = (STATE_DTYPE.itemsize, HIST_DTYPE.itemsize)
 
 

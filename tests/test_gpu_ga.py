@@ -211,10 +211,10 @@ def test_device_ga_fitness_matches_reevaluation(sgmm, tmp_path):
     for g in range(6):
         sess.step(g)
         torch.cuda.synchronize()
-        f, t = sgmm.evaluate_individual(sess.master.cpu(), None, tr, 0.0005, 0.001, 0.0, st)
-        row = sess.hist[g].cpu().numpy().view(HIST_DTYPE)[0]
+        f, t = sgmm.evaluate_individual(sess.masters[0].cpu(), None, tr, 0.0005, 0.001, 0.0, st)
+        row = sess.hist[0, g].cpu().numpy().view(HIST_DTYPE)[0]
         assert f == row["train_f"] and t == row["train_trades"]
-        fv, _ = sgmm.evaluate_individual(sess.master.cpu(), None, va, 0.0005, 0.001, 0.0, st)
+        fv, _ = sgmm.evaluate_individual(sess.masters[0].cpu(), None, va, 0.0005, 0.001, 0.0, st)
         assert fv == row["val_f"]
     pol, hist = sess.finish()
     fv, _ = sgmm.evaluate_individual(pol.get_weights(), None, va, 0.0005, 0.001, 0.0, st)
@@ -260,6 +260,139 @@ def test_ga_step_sharded_records_equal_contiguous(sgmm, arl):
         assert (a is None and b is None) or torch.equal(a, b)
     s = _read_state(runs[0][0])
     assert s["best_idx"] == 7 and s["adv_best_idx"] == int(np.argmax(-f))
+
+
+def _one_population(sgmm, arl):
+    """Fresh device state of one population for the direct entry-point tests:
+    P = 24, H = 16, 130 training + 70 validation ticks (the last 64-tick chunk
+    of each is partial), 48 episodes -- one 1024-thread scan workgroup each,
+    whose last one runs the fused tail.  Every call builds the identical state."""
+    from types import SimpleNamespace
+    from sgmm_amd import _lib
+    from sgmm_amd.model import genome_size
+    P, H, seed, gens = 24, 16, 42, 2
+    tr, va, stats = _bundles(8, T=130, Tv=70)
+    ticks = sgmm.TickStore()
+    o_tr, T = ticks.segments[ticks.add(tr, stats)]
+    o_va, Tv = ticks.segments[ticks.add(va, stats)]
+    ticks.to(DEV)
+    idx = np.arange(P)
+    eps = sgmm.EpisodeBatch(np.tile(idx, 2), np.repeat([o_tr, o_va], P), np.repeat([T, Tv], P), np.zeros(2 * P),
+                            adv=np.concatenate([idx, np.full(P, -1)]) if arl else None).to(DEV)
+    L, st = _state(sgmm, patience=4)
+    torch.manual_seed(2)
+    r = SimpleNamespace(L=L, P=P, H=H, seed=seed, gens=gens, arl=arl, ticks=ticks, eps=eps, st=st)
+    r.params = sgmm.params_tensor([sgmm.EnvConfig(phi=0.0005, tick_size=0.001)], DEV)
+    r.master = (0.1 * torch.randn(genome_size(H))).to(DEV)
+    r.madv = (0.1 * torch.randn(1250)).to(DEV) if arl else None
+    r.best = torch.zeros(genome_size(H), device=DEV)
+    r.hist = torch.zeros((gens, 40), dtype=torch.uint8, device=DEV)
+    r.seeds = torch.tensor([seed], dtype=torch.int64).to(DEV)
+    r.f = torch.zeros(2 * P, dtype=torch.float64, device=DEV)
+    r.t = torch.zeros(2 * P, dtype=torch.int32, device=DEV)
+    r.ws = sgmm.RolloutEngine(DEV).workspace(eps, arl)
+    r.pops = _lib.Populations(1, P, H, gens, st.data_ptr(), r.master.data_ptr(), r.madv.data_ptr() if arl else None,
+                              r.best.data_ptr(), r.seeds.data_ptr(), r.hist.data_ptr(), None)
+    return r
+
+
+def _bytes(r, names):
+    torch.cuda.synchronize()
+    return {n: getattr(r, n).cpu().numpy().tobytes() for n in names if getattr(r, n) is not None}
+
+
+@pytest.mark.parametrize("arl", [False, True])
+def test_generation_equals_generation_multi_of_one(sgmm, arl):
+    """sgmm_generation == sgmm_generation_multi with n_pop = 1 and seeds[0] = seed,
+    byte for byte over two generations: fitness, trades, GA state, master,
+    adversary master, best master and the history rows."""
+    import ctypes
+    from sgmm_amd import _lib
+    from sgmm_amd.drl_engine import HIST_DTYPE
+    ptr, s = _lib.ptr, _lib.stream_ptr()
+    out = []
+    for multi in (False, True):
+        r = _one_population(sgmm, arl)
+        tk, ep = r.ticks.struct(), r.eps.struct()
+        for _ in range(r.gens):
+            if multi:
+                rc = r.L.sgmm_generation_multi(ctypes.byref(tk), ctypes.byref(ep), ptr(r.params), ctypes.byref(r.pops),
+                                               ptr(r.f), ptr(r.t), ptr(r.ws), r.ws.numel(), s)
+            else:
+                rc = r.L.sgmm_generation(ctypes.byref(tk), ctypes.byref(ep), ptr(r.params), ptr(r.st), ptr(r.master),
+                                         ptr(r.madv), ptr(r.best), r.H, r.seed, r.P, ptr(r.f), ptr(r.t),
+                                         ptr(r.hist), r.gens, ptr(r.ws), r.ws.numel(), s)
+            _lib.check(rc, "generation")
+        out.append(_bytes(r, ("f", "t", "st", "master", "madv", "best", "hist")))
+    assert out[0].keys() == out[1].keys() and ("madv" in out[0]) == arl
+    for name in out[0]:
+        assert out[0][name] == out[1][name], name
+    # the run is live: both history rows written, the last one from the records left behind
+    rows = r.hist.cpu().numpy().view(HIST_DTYPE).reshape(-1)
+    f = r.f.cpu().numpy()
+    assert _read_state(r.st)["gen"] == r.gens and rows[1]["train_f"] == f[:r.P].max()
+    assert rows[1]["val_f"] == f[r.P + int(rows[1]["best_idx"])]
+
+
+@pytest.mark.parametrize("arl", [False, True])
+def test_rollout_asked_equals_asked_multi_of_one(sgmm, arl):
+    """sgmm_rollout_fitness_asked == sgmm_rollout_fitness_asked_multi with
+    n_pop = 1, both asking the shard that starts at individual i0 = 5: fitness
+    and trades byte for byte."""
+    import ctypes
+    from sgmm_amd import _lib
+    ptr, s = _lib.ptr, _lib.stream_ptr()
+    i0 = 5
+    out = []
+    for multi in (False, True):
+        r = _one_population(sgmm, arl)
+        tk, ep = r.ticks.struct(), r.eps.struct()
+        if multi:
+            rc = r.L.sgmm_rollout_fitness_asked_multi(ctypes.byref(tk), ctypes.byref(ep), ptr(r.params),
+                                                      ctypes.byref(r.pops), i0, 2 * r.P, ptr(r.f), ptr(r.t),
+                                                      ptr(r.ws), r.ws.numel(), s)
+        else:
+            asked = _lib.AskedPopulation(r.st.data_ptr(), r.master.data_ptr(), r.madv.data_ptr() if arl else None,
+                                         r.seed, i0, 0)
+            rc = r.L.sgmm_rollout_fitness_asked(ctypes.byref(tk), ctypes.byref(ep), ptr(r.params),
+                                                ctypes.byref(asked), r.H, ptr(r.f), ptr(r.t), ptr(r.ws),
+                                                r.ws.numel(), s)
+        _lib.check(rc, "asked rollout")
+        out.append(_bytes(r, ("f", "t")))
+    assert out[0] == out[1]
+    assert len(set(r.f.cpu().numpy()[:r.P])) > 1  # distinct individuals were rolled out
+
+
+def test_materialised_session_large_genome(sgmm, tmp_path):
+    """hidden_dim=64 (a 4546-float genome, above the in-kernel GA step's 4096)
+    with rng="device": the materialised-population session (sgmm_ga_ask ->
+    rollout -> sgmm_ga_tell -> sgmm_ga_val_update).  Each history row equals
+    re-evaluating the master that generation produced, and fused validation
+    equals validation of the best: histories, weights, sigma."""
+    from sgmm_amd.drl_engine import HIST_DTYPE, TrainingSession
+    tr, va, st = _bundles(8, T=130, Tv=70)
+    res = []
+    for val_mode in ("fused", "best"):
+        torch.manual_seed(6)
+        eng = sgmm.DRLEngine(pop_size=8, phi=0.0005, tick_size=0.001, save_dir=str(tmp_path / val_mode),
+                             hidden_dim=64, rng="device", seed=13, val_mode=val_mode, verbose=False)
+        sess = eng.session(tr, va, st, generations=5)
+        assert isinstance(sess, TrainingSession)
+        for g in range(5):
+            sess.step(g)
+            torch.cuda.synchronize()
+            master = sess.masters[0].cpu()
+            row = sess.hist[0, g].cpu().numpy().view(HIST_DTYPE)[0]
+            f, t = sgmm.evaluate_individual(master, None, tr, 0.0005, 0.001, 0.0, st)
+            assert f == row["train_f"] and t == row["train_trades"], (val_mode, g)
+            fv, _ = sgmm.evaluate_individual(master, None, va, 0.0005, 0.001, 0.0, st)
+            assert fv == row["val_f"], (val_mode, g)
+        pol, hist = sess.finish()
+        res.append((hist, pol.get_weights().numpy(), eng.mm_evolver.sigma))
+    (h0, w0, s0), (h1, w1, s1) = res
+    for k in h0:
+        assert np.array_equal(np.array(h0[k], np.float64), np.array(h1[k], np.float64)), k
+    assert np.array_equal(w0, w1) and s0 == s1
 
 
 def _fill(recs, f, t, vf, vt, P, W):

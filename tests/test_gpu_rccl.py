@@ -106,7 +106,7 @@ def test_rccl_single_population_session(sgmm, tmp_path, nccl_world1):
         sess.steps(0, 16)
         if ex == "always":
             assert sess.full_graph, getattr(sess, "capture_error", "")
-        assert sess.best_step == (vm == "best")
+        assert sess.best_val == (vm == "best")
         pol, hist = sess.finish()
         out[ex + vm] = (pol.get_weights().numpy(), hist, e.mm_evolver.sigma)
     wa, ha, sa = out["autofused"]

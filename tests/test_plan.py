@@ -85,6 +85,24 @@ ROWS = [
 ]
 
 
+def one_population(P, H, arl, tail):
+    """The launches of one population's 130 / 70-tick generation, as the
+    single-population entry points describe them (pop_eps = src_pop_eps = 0)
+    and as the sgmm_populations entries do with n_pop = 1 (= the launch's n):
+    tail: sgmm_generation / sgmm_generation_multi (P training + P validation
+    episodes, the whole generation's tail, mode 0); else the untailed asked
+    rollout of sgmm_rollout_fitness_asked / _multi."""
+    d = dict(n=2 * P, len=130, steps=P * 200, nsi=5, H=H, arl=arl, simds=1024, tail=tail, mode=0)
+    return dict(d, pop_eps=0, src_pop_eps=0), dict(d, pop_eps=2 * P if tail else 0, src_pop_eps=2 * P)
+
+
+# (name, the single-population launch, the same launch through sgmm_populations)
+ONE_POP = [(f"P{P}_h{H}_arl{arl}_{'tail' if tail else 'asked'}",) + one_population(P, H, arl, tail)
+           for P in (1, 24, 257, 600, 1100) for H in (16, 64) for arl in (0, 1) for tail in (1, 0)]
+LAUNCHES = [(name, spec) for name, spec, _ in ROWS] + \
+    [(f"{name}_{i}", spec) for name, *specs in ONE_POP for i, spec in enumerate(specs)]
+
+
 @pytest.fixture(scope="module")
 def plan_rows(tmp_path_factory):
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
@@ -92,12 +110,12 @@ def plan_rows(tmp_path_factory):
     exe = tmp_path_factory.mktemp("plan") / "plan_check"
     subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", f"-I{CSRC}", "-o", str(exe),
                     str(ROOT / "tests" / "plan_check.cpp")], check=True)
-    text = "".join(" ".join(f"{k}={v}" for k, v in spec.items()) + "\n" for _, spec, _ in ROWS)
+    text = "".join(" ".join(f"{k}={v}" for k, v in spec.items()) + "\n" for _, spec in LAUNCHES)
     run = subprocess.run([str(exe)], input=text, capture_output=True, text=True)
     assert run.returncode == 0, run.stderr  # a layout violation names the section and the launch
     lines = run.stdout.splitlines()
-    assert len(lines) == len(ROWS)
-    return {name: dict(tok.split("=") for tok in line.split()) for (name, _, _), line in zip(ROWS, lines)}
+    assert len(lines) == len(LAUNCHES)
+    return {name: dict(tok.split("=") for tok in line.split()) for (name, _), line in zip(LAUNCHES, lines)}
 
 
 @pytest.mark.parametrize("name,want", [(r[0], r[2]) for r in ROWS], ids=[r[0] for r in ROWS])
@@ -108,6 +126,15 @@ def test_plan_row(plan_rows, name, want):
 
 def test_groups17_is_the_default_plan(plan_rows):
     assert plan_rows["groups17"] == plan_rows["config3"]
+
+
+@pytest.mark.parametrize("name", [r[0] for r in ONE_POP])
+def test_one_population_plans_alike_through_either_entry(plan_rows, name):
+    """pop_eps reaches the plan only through the mode-3 tail's rules (the lanes
+    scan, the walk-order feedback), so a population driven through the
+    sgmm_populations entries with n_pop = 1 launches what the single-population
+    entries launch: the same kernels, groups, scan and workspace layout."""
+    assert plan_rows[f"{name}_0"] == plan_rows[f"{name}_1"]
 
 
 def _dummy_batch(_lib, n, length, adv):
