@@ -450,8 +450,10 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4))) void
         uint32_t mcnt = 0;
         bool merged = __builtin_popcount(sset) <= 1;
         int kc = merged ? 0 : CL;  // merge offset (CL: never)
-        // (a split wave's idle lanes read the episode's first tick)
-        auto tick_of = [&](int tt) { return tb + (LS == 1 || ntl > 0 ? t0 : 0) + min(tt, max(ntl - 1, 0)); };
+        // (an idle lane -- its chunk past the episode's last one, or a split wave's spare
+        // lane -- reads the episode's first tick: t0 >= T there, up to 63 chunks past
+        // the episode and possibly past the end of the tick columns)
+        auto tick_of = [&](int tt) { return tb + (ntl > 0 ? t0 : 0) + min(tt, max(ntl - 1, 0)); };
 #ifdef SGMM_STAMPS
         unsigned long long lite_t0, lite_sl = 0, lite_ts = 0, lite_s8 = 0, lite_s16 = 0;
         asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(lite_t0)::"memory");

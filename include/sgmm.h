@@ -252,7 +252,22 @@ int sgmm_rule_trace(const sgmm_ticks *ticks, const sgmm_episodes *eps,
  * regenerate any individual).  sigma and gen are read ON DEVICE from `state`
  * (stream_id 0: sigma_mm, 1: sigma_adv; gen = state->gen), so a generation's
  * launches have fixed arguments and can be captured once in a HIP graph and
- * replayed.  out row stride out_stride. */
+ * replayed.  out row stride out_stride.
+ *
+ * The stream is a contract (it is what lets any rank regenerate any individual;
+ * tests/ga_model.py restates it in numpy):
+ *   - parameter k of individual j takes output k % 4 of the Philox4x32-10 block
+ *     with counter words (k / 4, j, (uint32_t)gen, stream_id) and key words
+ *     (seed & 0xffffffff, seed >> 32); j = i0 + i is the global index;
+ *   - the four raw words r0..r3 become float32 uniforms
+ *       u0 = min(((float)r0 + 1) * 2^-32, 1)  in (0, 1],   u1 = (float)r1 * 2^-32,
+ *     and u2, u3 likewise from r2, r3 ((float)r rounds to nearest: every word
+ *     >= 0xffffff80 gives u0 = 1, z = 0);
+ *   - outputs 0, 1 = m * cos(2 pi u1), m * sin(2 pi u1) with m = sqrt(-2 ln u0),
+ *     outputs 2, 3 the same from (u2, u3), evaluated in float32 (logf, sqrtf,
+ *     sincospif); |z| <= sqrt(64 ln 2) = 6.66;
+ *   - out = master + (z * (float)sigma): a float32 multiply, then a float32 add
+ *     (model.py:69-70), never fused. */
 /* Device GA bookkeeping state (DRLEngine.train locals, drl_engine.py:84-89,
  * 143-160).  Initialise with sgmm_ga_state_init. */
 typedef struct sgmm_ga_state {

@@ -99,7 +99,109 @@ def one_population(P, H, arl, tail):
 # (name, the single-population launch, the same launch through sgmm_populations)
 ONE_POP = [(f"P{P}_h{H}_arl{arl}_{'tail' if tail else 'asked'}",) + one_population(P, H, arl, tail)
            for P in (1, 24, 257, 600, 1100) for H in (16, 64) for arl in (0, 1) for tail in (1, 0)]
-LAUNCHES = [(name, spec) for name, spec, _ in ROWS] + \
+
+
+# ------------------------------------------------------------------ the generation-boundary tail matrix
+# The launches of tests/test_gpu_ga_boundary.py part (c): H = 16, 12-tick
+# training and 8-tick validation episodes, the row named as the GPU test's id.
+# Each row pins the policy kernel, the scan (whose last workgroup runs the
+# boundary), its workgroup and the lanes per workgroup, so the matrix provably
+# reaches every tail path: the whole boundary (mode 0) is ga_step_fused when
+# P <= threads and ga_step_dev beyond; the tell's argmax (mode 3) is tell_wave in
+# the one-wave scan (table / frontier), the lanes scan, the frontier's fused scan
+# and the adversary scan; mode 4 is the validation launch that follows it.
+def whole(P, K, arl=0, **knobs):
+    """sgmm_generation (K = 1) / sgmm_generation_multi: P training + P validation episodes per population"""
+    pop = 0 if K == 1 else 2 * P
+    return dict(n=2 * P * K, len=12, steps=20 * P * K, nsi=5, H=16, arl=arl, simds=1024, tail=1, mode=0, pop_eps=pop,
+                src_pop_eps=pop, **knobs)
+
+
+def best_train(P, arl=0, **knobs):
+    """sgmm_generation_multi_best's training launch, 3 populations"""
+    return dict(n=3 * P, len=12, steps=36 * P, nsi=5, H=16, arl=arl, simds=1024, tail=1, mode=3, pop_eps=P,
+                src_pop_eps=P, **knobs)
+
+
+def best_val(**knobs):
+    """... and its validation launch: one episode per population"""
+    return dict(n=3, len=8, steps=24, nsi=5, H=16, arl=0, simds=1024, tail=1, mode=4, pop_eps=1, src_pop_eps=1, **knobs)
+
+
+def pin(policy, scan, threads, lanes_w=0, **more):
+    return dict(policy=policy, scan=scan, threads=threads, lanes_w=lanes_w, **more)
+
+
+WAVE_TABLE = dict(policy_path=2, scan_threads=64)
+WAVE_FRONTIER = dict(policy_path=1, groups=1, scan_threads=64, lanes_scan=0, fused_scan=0)
+LANES = dict(policy_path=1, groups=1, lanes_scan=1, fused_scan=0, seq_sum=1)
+FUSED = dict(policy_path=1, groups=1, fused_scan=1)
+BOUNDARY_ROWS = [
+    # mode 0, one population (n = 2 P): <= 256 one-chunk episodes take the state-parallel
+    # table, from 512 episodes the frontier kernel; 1024 scan threads up to 256 episodes,
+    # one wave beyond 512, or the forced width
+    ("default_P24-generation", whole(24, 1), pin("TableSp", "Wave", 1024)),
+    ("w64_P64-generation", whole(64, 1, scan_threads=64), pin("TableSp", "Wave", 64)),
+    ("w64_P65-generation", whole(65, 1, scan_threads=64), pin("TableSp", "Wave", 64)),
+    ("w256_P256-generation", whole(256, 1, scan_threads=256), pin("Frontier", "Wave", 256)),
+    ("w256_P257-generation", whole(257, 1, scan_threads=256), pin("Frontier", "Wave", 256)),
+    ("w512_P512-generation", whole(512, 1, scan_threads=512), pin("Frontier", "Wave", 512)),
+    ("w512_P513-generation", whole(513, 1, scan_threads=512), pin("Frontier", "Wave", 512)),
+    ("default_P600-generation", whole(600, 1), pin("Frontier", "Wave", 64)),
+    ("default_P1100-generation", whole(1100, 1), pin("Frontier", "Wave", 64)),
+    # the adversary scan ignores the width knob: 1024 threads up to 1024 episodes, 256 beyond
+    ("arl_P24-generation", whole(24, 1, arl=1), pin("TableMfma", "Arl", 1024)),
+    ("arl_P600-generation", whole(600, 1, arl=1), pin("TableMfma", "Arl", 256)),
+    # mode 0, three populations (n = 6 P): above 256 chunks the v3 table
+    ("default_P24-multi3", whole(24, 3), pin("TableSp", "Wave", 1024)),
+    ("w64_P64-multi3", whole(64, 3, scan_threads=64), pin("TableV3", "Wave", 64)),
+    ("w64_P65-multi3", whole(65, 3, scan_threads=64), pin("TableV3", "Wave", 64)),
+    ("w256_P256-multi3", whole(256, 3, scan_threads=256), pin("Frontier", "Wave", 256)),
+    ("w256_P257-multi3", whole(257, 3, scan_threads=256), pin("Frontier", "Wave", 256)),
+    ("w512_P512-multi3", whole(512, 3, scan_threads=512), pin("Frontier", "Wave", 512)),
+    ("w512_P513-multi3", whole(513, 3, scan_threads=512), pin("Frontier", "Wave", 512)),
+    ("default_P600-multi3", whole(600, 3), pin("Frontier", "Wave", 64)),
+    ("default_P1100-multi3", whole(1100, 3), pin("Frontier", "Wave", 64)),
+    ("arl_P24-multi3", whole(24, 3, arl=1), pin("TableMfma", "Arl", 1024)),
+    ("arl_P600-multi3", whole(600, 3, arl=1), pin("TableMfma", "Arl", 256)),
+    # mode 3 (n = 3 P), the one-wave scan after the table ...
+    ("wave_table_P24", best_train(24, **WAVE_TABLE), pin("TableSp", "Wave", 64)),
+    ("wave_table_P64", best_train(64, **WAVE_TABLE), pin("TableSp", "Wave", 64)),
+    ("wave_table_P65", best_train(65, **WAVE_TABLE), pin("TableSp", "Wave", 64)),
+    ("wave_table_P1024", best_train(1024, **WAVE_TABLE), pin("TableV3", "Wave", 64)),
+    ("wave_table_P1025", best_train(1025, **WAVE_TABLE), pin("TableV3", "Wave", 64)),
+    ("wave_table_P1100", best_train(1100, **WAVE_TABLE), pin("TableV3", "Wave", 64)),
+    # ... and after the frontier kernel (lanes and fused scans off)
+    ("wave_frontier_P24", best_train(24, **WAVE_FRONTIER), pin("Frontier", "Wave", 64)),
+    ("wave_frontier_P64", best_train(64, **WAVE_FRONTIER), pin("Frontier", "Wave", 64)),
+    ("wave_frontier_P65", best_train(65, **WAVE_FRONTIER), pin("Frontier", "Wave", 64)),
+    ("wave_frontier_P1024", best_train(1024, **WAVE_FRONTIER), pin("Frontier", "Wave", 64)),
+    ("wave_frontier_P1025", best_train(1025, **WAVE_FRONTIER), pin("Frontier", "Wave", 64)),
+    ("wave_frontier_P1100", best_train(1100, **WAVE_FRONTIER), pin("Frontier", "Wave", 64)),
+    # the lanes scan (populations of whole workgroups): 4 episodes per workgroup below 2 048 episodes, 2 from there
+    ("lanes_P24", best_train(24, **LANES), pin("Frontier", "Lanes", 256, 4)),
+    ("lanes_P64", best_train(64, **LANES), pin("Frontier", "Lanes", 256, 4)),
+    ("lanes_P1024", best_train(1024, **LANES), pin("Frontier", "Lanes", 128, 2)),
+    ("lanes_P1100", best_train(1100, **LANES), pin("Frontier", "Lanes", 128, 2)),
+    # the scan fused into the frontier walks: no scan launch, no scan workgroup
+    ("fused_P24", best_train(24, **FUSED), pin("Frontier", "Fused", 0)),
+    ("fused_P64", best_train(64, **FUSED), pin("Frontier", "Fused", 0)),
+    ("fused_P65", best_train(65, **FUSED), pin("Frontier", "Fused", 0)),
+    ("fused_P1024", best_train(1024, **FUSED), pin("Frontier", "Fused", 0)),
+    ("fused_P1025", best_train(1025, **FUSED), pin("Frontier", "Fused", 0)),
+    ("fused_P1100", best_train(1100, **FUSED), pin("Frontier", "Fused", 0)),
+    # the adversary scan
+    ("arl_table_P24", best_train(24, arl=1), pin("TableMfma", "Arl", 1024)),
+    ("arl_table_P1025", best_train(1025, arl=1), pin("TableMfma", "Arl", 256)),
+    # mode 4 under each knob set: three episodes, never the lanes or the fused scan
+    ("wave_table_val", best_val(**WAVE_TABLE), pin("TableSp", "Wave", 64, validation=1)),
+    ("wave_frontier_val", best_val(**WAVE_FRONTIER), pin("Frontier", "Wave", 64, validation=1)),
+    ("lanes_val", best_val(**LANES), pin("Frontier", "Wave", 1024, validation=1)),
+    ("fused_val", best_val(**FUSED), pin("Frontier", "Wave", 1024, validation=1)),
+    ("arl_table_val", best_val(), pin("TableSp", "Wave", 1024, validation=1)),
+]
+
+LAUNCHES = [(name, spec) for name, spec, _ in ROWS + BOUNDARY_ROWS] + \
     [(f"{name}_{i}", spec) for name, *specs in ONE_POP for i, spec in enumerate(specs)]
 
 
@@ -122,6 +224,39 @@ def plan_rows(tmp_path_factory):
 def test_plan_row(plan_rows, name, want):
     got = plan_rows[name]
     assert {k: got[k] for k in want} == {k: str(v) for k, v in want.items()}, got
+
+
+@pytest.mark.parametrize("name,want", [(r[0], r[2]) for r in BOUNDARY_ROWS], ids=[r[0] for r in BOUNDARY_ROWS])
+def test_boundary_tail_plan_row(plan_rows, name, want):
+    got = plan_rows[name]
+    assert {k: got[k] for k in want} == {k: str(v) for k, v in want.items()}, got
+
+
+def test_boundary_tail_matrix_is_pinned():
+    """Every (shape, knobs) the GPU boundary tests launch has its row above, with the same knobs."""
+    import test_gpu_ga_boundary as b
+    from sgmm_pkg import load
+    paths = load()._lib.POLICY_PATHS
+    rows = {name: spec for name, spec, _ in BOUNDARY_ROWS}
+    shape = {"n", "len", "steps", "nsi", "H", "arl", "simds", "tail", "mode", "pop_eps", "src_pop_eps"}
+
+    def knobs_of(spec):
+        return {k: v for k, v in spec.items() if k not in shape}
+
+    def numeric(knobs):
+        return {k: paths[v] if k == "policy_path" else v for k, v in knobs.items()}
+
+    for name, (P, knobs, arl) in b.TAIL_WHOLE.items():
+        for K, tag in ((1, "generation"), (3, "multi3")):
+            spec = rows[f"{name}-{tag}"]
+            assert (spec["n"], spec["arl"], spec["mode"]) == (2 * P * K, int(arl), 0) and knobs_of(spec) == numeric(knobs)
+    for name, (P, knobs, arl) in b.TAIL_BEST.items():
+        spec = rows[name]
+        assert (spec["n"], spec["arl"], spec["mode"]) == (3 * P, int(arl), 3) and knobs_of(spec) == numeric(knobs)
+    for kind, knobs in b.BEST_KNOBS.items():
+        assert knobs_of(rows[f"{kind}_val"]) == numeric(knobs) and rows[f"{kind}_val"]["mode"] == 4
+    assert len(rows) == 2 * len(b.TAIL_WHOLE) + len(b.TAIL_BEST) + len(b.BEST_KNOBS)
+    assert (b.T_TRAIN, b.T_VAL, b.H) == (12, 8, 16)
 
 
 def test_groups17_is_the_default_plan(plan_rows):
