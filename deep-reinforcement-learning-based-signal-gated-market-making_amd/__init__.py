@@ -4,7 +4,7 @@ Drop-in for the hot path of KAS-W/Deep-Reinforcement-Learning-Based-Signal-
 Gated-Market-Making: FTPEnv (Env/market_env.py), TradingPolicy /
 AdversaryPolicy / NeuroEvolution (models/model.py), evaluate_individual /
 DRLEngine (Env/drl_engine.py), FOICPolicy / GLFTPolicy (Env/benchmarks.py) and the
-evaluation numbers of analytics/mm_analyzer.py; pipeline/agent_trainer.py then runs unchanged
+evaluation numbers of analytics/mm_analyzer.py and the hypothesis tests of main.py; pipeline/agent_trainer.py then runs unchanged
 on top of them (see dropin/ and INTEGRATION.md).  Compute runs in libsgmm.so (HIP, gfx950).
 
 The directory name carries hyphens, so import it through the repository's
@@ -17,7 +17,8 @@ from .model import (AdversaryPolicy, NeuroEvolution, TradingPolicy, genome_size,
 from .rollout import (EnvConfig, EpisodeBatch, RolloutEngine, TickStore,  # noqa: F401
                       adversary_forward, normalize_signals, params_tensor, policy_forward)
 from .benchmarks import FOICPolicy, GLFTPolicy, quote_rule  # noqa: F401
-from .analytics import summarize, summary_from_frame  # noqa: F401
+from .analytics import (dm_test, durbin_watson, get_mbb_sharpe, hypothesis_report, mbb_sharpe,  # noqa: F401
+                        summarize, summary_from_frame)
 from .recorder import run_benchmark_and_save, run_rule_backtests  # noqa: F401
 from .drl_engine import DRLEngine, MultiDRLEngine, evaluate_individual, evaluate_population  # noqa: F401
 

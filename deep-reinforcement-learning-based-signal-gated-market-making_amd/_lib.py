@@ -101,7 +101,20 @@ class EpisodeSummary(ctypes.Structure):
                                        "reserved")]
 
 
+class DMResult(ctypes.Structure):
+    """sgmm_dm_result: Diebold-Mariano statistic of one series."""
+    _fields_ = [(n, ctypes.c_double) for n in ("stat", "p_value", "mean_d", "var_d")] + [("n", ctypes.c_int64)]
+
+
+class MBBResult(ctypes.Structure):
+    """sgmm_mbb_result: block-bootstrap Sharpe ratio of one wealth series."""
+    _fields_ = [(n, ctypes.c_double) for n in ("mean_sr", "ci_lo", "ci_hi")] + \
+        [(n, ctypes.c_int32) for n in ("n_returns", "num_blocks", "zero_replicates", "flags")]
+
+
 assert ctypes.sizeof(EnvParams) == 48
+assert ctypes.sizeof(DMResult) == 40
+assert ctypes.sizeof(MBBResult) == 40
 assert ctypes.sizeof(QuoteRule) == 144
 assert ctypes.sizeof(EpisodeSummary) == 96
 assert ctypes.sizeof(GAState) == 80
@@ -129,6 +142,10 @@ SIGNATURES = {
                                             _VP, _I64, _I32, _VP, _VP, _I32, _VP, _VP]),
     "sgmm_rule_trace": (ctypes.c_int, [ctypes.POINTER(Ticks), ctypes.POINTER(Episodes), _VP,
                                        _VP, _VP, _I32] + [_VP] * 12),
+    "sgmm_trace_wealth": (ctypes.c_int, [ctypes.POINTER(Ticks), ctypes.POINTER(Episodes), _VP, _VP, _VP, _VP]),
+    "sgmm_durbin_watson": (ctypes.c_int, [_VP, _VP, _VP, _I32, _VP, _VP]),
+    "sgmm_dm_test": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _VP, _VP]),
+    "sgmm_mbb_sharpe": (ctypes.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _I64, _U64, _VP, _VP, _VP, _VP, _VP]),
     "sgmm_ga_ask": (ctypes.c_int, [_VP, _I64, _VP, _U32, _U64, _I32, _I32, _VP, _I64, _VP]),
     "sgmm_ga_state_init": (ctypes.c_int, [_VP, _D, _I32, _D, _VP]),
     "sgmm_ga_tell": (ctypes.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I64, _VP, _VP, _I64, _I64,

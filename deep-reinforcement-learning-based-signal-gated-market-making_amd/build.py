@@ -16,7 +16,7 @@ from pathlib import Path
 
 PKG_DIR = Path(__file__).resolve().parent
 SOURCES = ["csrc/sgmm_capi.hip", "csrc/sgmm_rollout.hip", "csrc/sgmm_frontier.hip", "csrc/sgmm_ga.hip",
-           "csrc/sgmm_bundle.hip", "csrc/sgmm_sgu2.hip", "csrc/sgmm_evaluate.hip"]
+           "csrc/sgmm_bundle.hip", "csrc/sgmm_sgu2.hip", "csrc/sgmm_evaluate.hip", "csrc/sgmm_hypothesis.hip"]
 HEADERS = ["csrc/sgmm_device.h", "csrc/sgmm_internal.h", "csrc/sgmm_ga_device.h", "csrc/sgmm_rollout.h",
            "csrc/sgmm_plan.h",           "../include/sgmm.h"]
 ARCH = os.environ.get("SGMM_OFFLOAD_ARCH", "gfx950")

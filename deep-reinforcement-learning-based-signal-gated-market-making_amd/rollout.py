@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import EnvParams, EpisodeSummary, Episodes, QuoteRule, Ticks, check, ptr, stream_ptr
+from ._lib import (DMResult, EnvParams, EpisodeSummary, Episodes, MBBResult, QuoteRule, Ticks, check, ptr,
+                   stream_ptr)
 
 ENV_PARAMS_DTYPE = np.dtype([("phi", "<f8"), ("tick", "<f8"), ("fee", "<f8"),
                              ("idle_penalty", "<f8"), ("i_max", "<i4"), ("i_min", "<i4"),
@@ -28,6 +29,12 @@ SUMMARY_DTYPE = np.dtype([(k, "<f8") for k in ("total_pnl", "map", "pnl_to_map",
                          [(k, "<i4") for k in ("trade_rows", "fills_buy", "fills_sell", "final_inventory",
                                                "steps", "reserved")])
 assert SUMMARY_DTYPE.itemsize == ctypes.sizeof(EpisodeSummary) == 96
+DM_DTYPE = np.dtype([(k, "<f8") for k in ("stat", "p_value", "mean_d", "var_d")] + [("n", "<i8")])
+MBB_DTYPE = np.dtype([(k, "<f8") for k in ("mean_sr", "ci_lo", "ci_hi")] +
+                     [(k, "<i4") for k in ("n_returns", "num_blocks", "zero_replicates", "flags")])
+assert DM_DTYPE.itemsize == ctypes.sizeof(DMResult) == 40
+assert MBB_DTYPE.itemsize == ctypes.sizeof(MBBResult) == 40
+MBB_CLAMPED, MBB_NOT_RESAMPLED = 1, 2
 RULE_TRACE_COLUMNS = ("off_a", "off_b", "inventory", "cash", "reward", "pnl", "fee_paid", "fill_buy", "fill_sell")
 
 COLUMNS = ("s1n", "s2n", "mid_next", "best_ask", "best_bid", "buy_max", "sell_min")
@@ -266,6 +273,109 @@ class RolloutEngine:
                                     stream_ptr(stream))
         check(rc, "sgmm_rule_trace")
         return fit, trd, tr
+
+
+    # ------------------------------------------------------------ hypothesis tests (main.py:227-297)
+    def wealth(self, ticks: TickStore, eps: EpisodeBatch, trace: dict, stream=None) -> torch.Tensor:
+        """The wealth column (Env/recorder.py:46) of a trace / trace_rules result,
+        f64[total_steps] on the device, rows step_off[e] + t."""
+        w = torch.empty(eps.total_steps, dtype=torch.float64, device=self.device)
+        tk, ep = ticks.struct(), eps.struct()
+        rc = self.L.sgmm_trace_wealth(ctypes.byref(tk), ctypes.byref(ep), ptr(trace["inventory"]),
+                                      ptr(trace["cash"]), ptr(w), stream_ptr(stream))
+        check(rc, "sgmm_trace_wealth")
+        return w
+
+    def _series(self, off, *values):
+        """Host and device copies of a series batch's offsets; the values are
+        checked to be contiguous float64 device tensors that cover them."""
+        off_h = np.ascontiguousarray(off, np.int64).reshape(-1)
+        if len(off_h) < 1:
+            raise ValueError("off: n_series + 1 offsets")
+        for v in values:
+            if v is None:
+                continue
+            if v.dtype != torch.float64 or v.dim() != 1 or not v.is_contiguous() or v.device.type != "cuda":
+                raise ValueError("series values: a contiguous 1-d float64 device tensor")
+            if len(off_h) > 1 and v.numel() < int(off_h.max()):
+                raise ValueError(f"series values hold {v.numel()} elements, off reaches {int(off_h.max())}")
+        # the device copy stays referenced until the next call: the launches read it
+        self._off_dev = torch.from_numpy(off_h).to(self.device)
+        return off_h, self._off_dev
+
+    def durbin_watson(self, values: torch.Tensor, off, stream=None) -> torch.Tensor:
+        """Durbin-Watson statistic of every series (sgmm_durbin_watson): f64[n] on the device."""
+        off_h, off_d = self._series(off, values)
+        n = len(off_h) - 1
+        out = torch.empty(n, dtype=torch.float64, device=self.device)
+        rc = self.L.sgmm_durbin_watson(ptr(values), ptr(off_d), off_h.ctypes.data, n, ptr(out), stream_ptr(stream))
+        check(rc, "sgmm_durbin_watson")
+        return out
+
+    def dm_test(self, actual: torch.Tensor, pred1: torch.Tensor, pred2: torch.Tensor | None, off,
+                crit: str = "MSE", stream=None):
+        """Diebold-Mariano test of every series (sgmm_dm_test); pred2 None = the
+        zero forecast.  crit as the reference: "MSE", anything else is MAD.
+        Returns the device tensor (n x 40 bytes) and its host copy as DM_DTYPE
+        records (the copy waits for the launch)."""
+        off_h, off_d = self._series(off, actual, pred1, pred2)
+        n = len(off_h) - 1
+        out = torch.empty((n, DM_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        rc = self.L.sgmm_dm_test(ptr(actual), ptr(pred1), ptr(pred2), ptr(off_d), off_h.ctypes.data, n,
+                                 0 if crit == "MSE" else 1, ptr(out), stream_ptr(stream))
+        check(rc, "sgmm_dm_test")
+        if stream is not None:
+            stream.synchronize()
+        return out, out.cpu().numpy().reshape(-1).view(DM_DTYPE)
+
+    def mbb_sharpe(self, wealth: torch.Tensor, off, block_size: int = 100, n_boot: int = 500, seed: int = 0,
+                   starts: torch.Tensor | None = None, want_starts: bool = False, stream=None) -> "MBBOutput":
+        """Moving-block bootstrap of the per-step Sharpe ratio of every wealth
+        series (sgmm_mbb_sharpe).  starts: int32 device tensor [n, n_boot, stride]
+        of block starts, or None for the device's Philox stream keyed by seed;
+        want_starts also returns the starts used.  Everything stays on the
+        device; MBBOutput.records() copies the 40-byte results back."""
+        off_h, off_d = self._series(off, wealth)
+        n = len(off_h) - 1
+        dv = self.device
+        stride = 0
+        if starts is not None:
+            if starts.dtype != torch.int32 or starts.dim() != 3 or not starts.is_contiguous() \
+                    or tuple(starts.shape[:2]) != (n, n_boot):
+                raise ValueError(f"starts: a contiguous int32 tensor [{n}, {n_boot}, stride]")
+            stride = int(starts.shape[2])
+        elif want_starts:
+            lens = np.diff(off_h)
+            stride = max(1, int(((lens.max() if n else 1) - 1) // max(block_size, 1)))
+        out = torch.empty((n, MBB_DTYPE.itemsize), dtype=torch.uint8, device=dv)
+        boot = torch.empty((n, max(n_boot, 0)), dtype=torch.float64, device=dv)
+        rets = torch.empty(max(int(off_h.max()), 1), dtype=torch.float64, device=dv)
+        used = torch.zeros((n, n_boot, stride), dtype=torch.int32, device=dv) if want_starts else None
+        rc = self.L.sgmm_mbb_sharpe(ptr(wealth), ptr(off_d), off_h.ctypes.data, n, block_size, n_boot, ptr(starts),
+                                    stride, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), ptr(out), ptr(boot),
+                                    ptr(used), ptr(rets), stream_ptr(stream))
+        check(rc, "sgmm_mbb_sharpe")
+        return MBBOutput(out, boot, rets, used, off_h, off_d, stream)
+
+
+@dataclass
+class MBBOutput:
+    """Device results of RolloutEngine.mbb_sharpe: result (n x 40 bytes,
+    sgmm_mbb_result), boot f64[n, n_boot], returns (series s's n_returns values
+    from off[s]) and, when asked for, the int32 starts used."""
+    result: torch.Tensor
+    boot: torch.Tensor
+    returns: torch.Tensor
+    starts: torch.Tensor | None
+    off: np.ndarray
+    off_dev: torch.Tensor
+    stream: object = None
+
+    def records(self) -> np.ndarray:
+        """Host copy of the results as MBB_DTYPE records (waits for the launches)."""
+        if self.stream is not None:
+            self.stream.synchronize()
+        return self.result.cpu().numpy().reshape(-1).view(MBB_DTYPE)
 
 
 def policy_forward(genomes: torch.Tensor, hidden: int, states: torch.Tensor,

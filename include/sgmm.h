@@ -246,6 +246,116 @@ int sgmm_rule_trace(const sgmm_ticks *ticks, const sgmm_episodes *eps,
                     uint8_t *fill_buy, uint8_t *fill_sell,
                     double *fitness, int32_t *trades, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Hypothesis tests of the evaluation stage (main.py:227-297): Diebold-Mariano
+ * (H1), Durbin-Watson (H2) and the moving-block bootstrap of the per-step
+ * Sharpe ratio (H3), batched over many series.
+ *
+ * A SERIES BATCH is (values, off, n_series): device doubles and a device
+ * int64 array of n_series + 1 offsets, series s = values[off[s] .. off[s+1]).
+ * off_host is an optional HOST copy of off (as rules_host above): when given,
+ * off_host[0] >= 0, non-decreasing offsets and series lengths below 2^31 are
+ * checked before any HIP call; NULL skips the check (a series whose offsets
+ * decrease is then read as empty).
+ *
+ * THE LANE SUM.  Every sum of these entry points is evaluated in one fixed
+ * order, which analytics.py restates in numpy: element i of the summed
+ * sequence belongs to lane i mod 64; a lane adds its elements in increasing
+ * i, starting from 0.0; the 64 lane values are combined by the xor butterfly
+ * d = 32, 16, 8, 4, 2, 1 (v += v[lane ^ d]).  A mean is that sum divided once
+ * by the count.  All float64, nothing fused.
+ * ------------------------------------------------------------------------ */
+
+/* wealth[step_off[e] + t] = cash[.] + (double)inventory[.] * mid_next[tick_off[e] + t]
+ * for every step of the batch (Env/recorder.py:46; the unfused expression of
+ * the episode summaries), from the cash / inventory columns of
+ * sgmm_rollout_trace or sgmm_rule_trace.  eps->step_off must be the exclusive
+ * prefix sum of eps->len.  One launch. */
+int sgmm_trace_wealth(const sgmm_ticks *ticks, const sgmm_episodes *eps,
+                      const int32_t *inventory, const double *cash, double *wealth,
+                      void *stream);
+
+/* statsmodels' durbin_watson (main.py:247): out[s] = sum_{t>=1} (e[t] - e[t-1])^2
+ * / sum_t e[t]^2, both lane sums (numerator element i = t - 1).  An empty
+ * series gives 0/0 = NaN, length 1 gives 0 / e^2.  out: double[n_series]. */
+int sgmm_durbin_watson(const double *values, const int64_t *off, const int64_t *off_host,
+                       int32_t n_series, double *out, void *stream);
+
+typedef struct sgmm_dm_result {
+    double  stat;      /* mean_d / sqrt(var_d / n) */
+    double  p_value;   /* 2 * (1 - Phi(|stat|)) */
+    double  mean_d, var_d;
+    int64_t n;
+} sgmm_dm_result;      /* 40 bytes */
+
+/* dm_test (main.py:228-236) of each series: actual, pred1, pred2 are series
+ * batches over the same off; pred2 may be NULL (zeros, the naive forecast of
+ * main.py:242).  crit 0 (MSE): e = (actual - pred)^2, crit 1 (MAD): e =
+ * |actual - pred|.  d = e1 - e2; mean_d = lane sum / n; var_d = lane sum of
+ * (d - mean_d)^2 divided by n - 1 (np.var, ddof = 1, two passes; NaN for
+ * n < 2); stat = mean_d / sqrt(var_d / n); p_value = 2 * (1 - Phi(|stat|))
+ * with Phi(x) = 0.5 * erfc((-x) / sqrt(2.0)).  NaN inputs propagate.  The
+ * reference's h argument is unused there and has no counterpart here. */
+int sgmm_dm_test(const double *actual, const double *pred1, const double *pred2,
+                 const int64_t *off, const int64_t *off_host, int32_t n_series, int32_t crit,
+                 sgmm_dm_result *out, void *stream);
+
+enum {
+    SGMM_MBB_CLAMPED = 1,      /* a caller's start lay outside [0, n - block_size] */
+    SGMM_MBB_NOT_RESAMPLED = 2 /* n <= block_size: the plain Sharpe ratio, no bootstrap */
+};
+
+typedef struct sgmm_mbb_result {
+    double  mean_sr, ci_lo, ci_hi;
+    int32_t n_returns;        /* returns left after the NaN drop */
+    int32_t num_blocks;       /* n_returns / block_size, 0 when not resampled */
+    int32_t zero_replicates;  /* replicates equal to 0 (std <= 1e-9 or NaN) */
+    int32_t flags;            /* SGMM_MBB_* */
+} sgmm_mbb_result;            /* 40 bytes */
+
+/* get_mbb_sharpe (main.py:251-285) of each WEALTH series: the moving-block
+ * bootstrap of the per-step Sharpe ratio, 1 <= n_boot <= 4096 replicates of
+ * n / block_size blocks of block_size >= 1 returns.
+ *   - returns: r[t] = w[t+1] / w[t] - 1 (a division, then a subtraction); NaN
+ *     entries are dropped in order, +-inf is kept (pct_change().dropna() for a
+ *     NaN-free wealth; pandas forward-fills a NaN wealth, which is outside the
+ *     parity domain).  n = the number kept.  `returns` is caller-owned device
+ *     memory for off[n_series] doubles, distinct from wealth: series s's
+ *     returns are left at returns[off[s] .. off[s] + n).
+ *   - n <= block_size (n = 0 included): sr = mean / std if std > 1e-9 else 0
+ *     over the returns; mean_sr = ci_lo = ci_hi = sr; flags has
+ *     SGMM_MBB_NOT_RESAMPLED; every replicate slot of boot is set to sr.
+ *   - otherwise replicate b concatenates blocks r[start .. start + block_size)
+ *     for its num_blocks starts; its value is mean / std (np.std: ddof = 0,
+ *     two passes, lane sums over the replicate's elements) if std > 1e-9,
+ *     else 0 -- a NaN std (an inf in the replicate) compares false and gives 0.
+ *     mean_sr = lane sum of the replicates / n_boot; ci_lo / ci_hi = the 2.5
+ *     and 97.5 percentiles by numpy's linear rule: virtual index v = (n_boot -
+ *     1) * (2.5 / 100) resp. (97.5 / 100), a = sorted[floor v], b = the next
+ *     one, t = v - floor v, value = a + (b - a) * t, or b - (b - a) * (1 - t)
+ *     when t >= 0.5; NaN if any replicate is NaN.
+ *   - starts: device int32 [n_series][n_boot][starts_stride], starts_stride >=
+ *     every resampled series' num_blocks; a start outside [0, n - block_size]
+ *     is clamped into it and SGMM_MBB_CLAMPED is set -- nothing outside the
+ *     series is ever read.  starts = NULL: block j of replicate b of series s
+ *     takes output j % 4 of Philox4x32-10 with counter words (j / 4, b, s, 2)
+ *     and key words (seed & 0xffffffff, seed >> 32) -- the generator of
+ *     sgmm_ga_ask, stream id 2 -- and start = ((uint64_t)word * (uint64_t)(n -
+ *     block_size + 1)) >> 32, whose bias is at most (n - block_size + 1) / 2^32.
+ *   - boot: caller-owned device double[n_series][n_boot], every replicate's
+ *     value (it carries them from the replicate launch to the percentile
+ *     launch, so it is not optional).  starts_out: optional device int32 in the
+ *     layout of starts, the starts actually used; entries past num_blocks are
+ *     not written.  starts and starts_out need off_host: their row stride is
+ *     checked against every series' possible block count before the launch.
+ * Three launches on `stream` (returns, replicates, percentiles), no
+ * cross-workgroup waits. */
+int sgmm_mbb_sharpe(const double *wealth, const int64_t *off, const int64_t *off_host,
+                    int32_t n_series, int32_t block_size, int32_t n_boot,
+                    const int32_t *starts, int64_t starts_stride, uint64_t seed,
+                    sgmm_mbb_result *out, double *boot, int32_t *starts_out, double *returns,
+                    void *stream);
+
 /* NeuroEvolution.ask (models/model.py:65-71) on device:
  * out[i,k] = master[k] + z(seed, stream_id, gen, i0+i, k) * (float)sigma,
  * z ~ N(0,1) from Philox4x32-10 + Box-Muller (counter-based, so any rank can

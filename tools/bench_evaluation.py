@@ -18,6 +18,16 @@ Kernel times are the library's own HIP events around each launch
 min and max over the repetitions are reported.  The summaries of the timed
 batch are also compared with the trace path's fitness (bit-equal or the run
 fails).
+
+The hypothesis tests (--only hypothesis runs these alone; written to
+profiles/hypothesis_bench.json):
+  mbb_main        sgmm_mbb_sharpe at main.py's shape: 4 series x 960 rows,
+                  block 100, 500 resamples (k_mbb_returns, k_mbb_replicates,
+                  k_mbb_reduce: the three launches timed by their own events)
+  mbb_sweep       the same at 2560 series x 912 rows
+  numpy loop      get_mbb_sharpe's loop in numpy on the host (one np.concatenate,
+                  np.std and np.mean per resample) for the 4 series, and for 64
+                  of the sweep's -- wall clock
 """
 from __future__ import annotations
 
@@ -55,6 +65,69 @@ def stats(ms):
     return {"median_ms": float(np.median(a)), "min_ms": float(a[0]), "max_ms": float(a[-1]), "reps": len(a)}
 
 
+def numpy_mbb(w, block_size=100, n_boot=500):
+    """main.py:251-285 in numpy: the loop a user runs on the host today."""
+    r = w[1:] / w[:-1] - 1.0
+    r = r[~np.isnan(r)]
+    n = len(r)
+    if n <= block_size:
+        sd = np.std(r)
+        sr = np.mean(r) / sd if sd > 1e-9 else 0
+        return sr, (sr, sr)
+    srs = []
+    for _ in range(n_boot):
+        idx = np.random.randint(0, n - block_size + 1, size=max(1, n // block_size))
+        x = np.concatenate([r[i:i + block_size] for i in idx])
+        sd = np.std(x)
+        srs.append(np.mean(x) / sd if sd > 1e-9 else 0)
+    return np.mean(srs), np.percentile(srs, [2.5, 97.5])
+
+
+def bench_hypothesis(a, sgmm, _lib, dev):
+    """The bootstrap at main.py's shape and at a sweep's; HIP events per launch."""
+    eng = sgmm.RolloutEngine(dev)
+    rng = np.random.default_rng(9)
+    kinds = ("mbb_returns", "mbb_replicates", "mbb_reduce")
+    res = {"device": torch.cuda.get_device_name(0), "block_size": 100, "n_boot": 500}
+    for name, n_series, rows, n_host in (("mbb_main", 4, 960, 4), ("mbb_sweep", a.episodes, a.ticks, 64)):
+        wealth = 100.0 + np.cumsum(rng.normal(0.01, 0.3, (n_series, rows)), axis=1)
+        w = torch.from_numpy(wealth.reshape(-1)).to(dev)
+        off = np.arange(n_series + 1, dtype=np.int64) * rows
+        for _ in range(a.warmup):
+            out = eng.mbb_sharpe(w, off, 100, 500, seed=1)
+        torch.cuda.synchronize()
+        _lib.profile_read()
+        ms = {k: [] for k in kinds + ("total",)}
+        _lib.profile_enable(True)
+        for _ in range(a.reps):
+            out = eng.mbb_sharpe(w, off, 100, 500, seed=1)
+            torch.cuda.synchronize()
+            got = {k: v[0] / v[1] for k, v in _lib.profile_read().items()}
+            for k in kinds:
+                ms[k].append(got[k])
+            ms["total"].append(sum(got[k] for k in kinds))
+        _lib.profile_enable(False)
+        rec = out.records()
+        nb = (rows - 1) // 100
+        reads = n_series * 500 * nb * 100 * 2 * 8
+        t0 = time.perf_counter()
+        host = [numpy_mbb(wealth[i]) for i in range(n_host)]
+        host_s = time.perf_counter() - t0
+        # same estimator, different random starts: the two means agree within the bootstrap's spread
+        gap = float(np.max(np.abs(rec["mean_sr"][:n_host] - np.array([h[0] for h in host]))))
+        med = float(np.median(ms["total"]))
+        res[name] = {"series": n_series, "rows": rows, **{k: stats(v) for k, v in ms.items()},
+                     "replicate_reads_bytes": reads,
+                     "replicate_read_TBps": reads / (float(np.median(ms["mbb_replicates"])) * 1e-3) / 1e12,
+                     "series_per_s": n_series / (med * 1e-3),
+                     "numpy_loop": {"series": n_host, "wall_s": host_s, "per_series_ms": 1e3 * host_s / n_host,
+                                    "max_abs_mean_gap_to_device": gap}}
+    print(json.dumps(res))
+    out_path = Path(a.hypothesis_out)
+    out_path.parent.mkdir(parents=True, exist_ok=True)
+    out_path.write_text(json.dumps(res, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--episodes", type=int, default=2560)
@@ -64,11 +137,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "evaluation_bench.json"))
+    ap.add_argument("--hypothesis-out", default=str(ROOT / "profiles" / "hypothesis_bench.json"))
+    ap.add_argument("--only", choices=("all", "evaluation", "hypothesis"), default="all")
     a = ap.parse_args()
     import sgmm_pkg
     sgmm = sgmm_pkg.load()
     from sgmm_amd import _lib, benchmarks, recorder, synthetic
     dev = torch.device("cuda:0")
+    if a.only != "evaluation":
+        bench_hypothesis(a, sgmm, _lib, dev)
+    if a.only == "hypothesis":
+        return
     E, T, H = a.episodes, a.ticks, a.hidden
     b = synthetic.bundle_510300(T, seed=4)
     st = synthetic.train_stats(b)
