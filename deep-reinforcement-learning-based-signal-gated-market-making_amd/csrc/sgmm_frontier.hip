@@ -8,7 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "sgmm_rollout.h"
+#include "sgmm_mlp_mfma.h"  // the spill kernel's MLP (with sgmm_rollout.h)
 
 namespace sgmm {
 
@@ -889,9 +889,10 @@ __device__ __forceinline__ uint64_t m_scan_seg(uint64_t m, int seg) {
 }
 template <int H, int NSI>
 __global__ __launch_bounds__(kWave * NSI) void k_frontier_spill(FrontierArgs args, int32_t n_waves, int32_t ls) {
-    static_assert(H % 16 == 0 && H <= 32, "spill: H = 16 or 32");
+    static_assert(H <= 32, "spill: H = 16 or 32");
+    using M = MlpMfma<H>;
     using L = GenomeLayout<H>;
-    constexpr int NT = H / 16, KS = H / 4, HP = H + 4;
+    constexpr int NT = M::NT, KS = M::KS, HP = M::HP;
     constexpr int kPer = 16;   // entries per thread and segment
     constexpr int kCap = 512;  // spilled waves per window
     const EpArrays& ep = args.ep;
@@ -907,7 +908,7 @@ __global__ __launch_bounds__(kWave * NSI) void k_frontier_spill(FrontierArgs arg
     __shared__ __attribute__((aligned(16))) float w3i[2 * H];
     __shared__ __attribute__((aligned(16))) float hb_s[NSI][kWave * HP];
     __shared__ __attribute__((aligned(16))) double rl_s[NSI][kWave];
-    __shared__ uint8_t to_s[NSI][kWave];  // successor state | traded << 7
+    __shared__ uint8_t to_s[NSI][kWave];  // pack_step of [state][lane]
     int staged = -1;                      // the episode whose genome is in gsm
     float w2f[NT][KS];
     f32x4 b2c[NT];
@@ -966,14 +967,8 @@ __global__ __launch_bounds__(kWave * NSI) void k_frontier_spill(FrontierArgs arg
                     __syncthreads();
                     stage_genomes(args.src, e, ep.genome[e], -1, L::N, gsm, nullptr);
                     __syncthreads();
-                    if (tid < 2 * H) w3i[tid] = gsm[L::W3 + (tid & 1) * H + (tid >> 1)];
-#pragma unroll
-                    for (int rt = 0; rt < NT; ++rt) {
-#pragma unroll
-                        for (int i = 0; i < KS; ++i) w2f[rt][i] = gsm[L::W2 + (16 * rt + col) * H + 4 * i + grp];
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) b2c[rt][r] = gsm[L::B2 + 16 * rt + 4 * grp + r];
-                    }
+                    M::store_w3i(gsm, w3i);
+                    M::load_w2(gsm, grp, col, w2f, b2c);
                     staged = e;
                     __syncthreads();
                 }
@@ -989,80 +984,36 @@ __global__ __launch_bounds__(kWave * NSI) void k_frontier_spill(FrontierArgs arg
                     };
                     const int si = wv;
                     float xs0[4], xs1[4];
-#pragma unroll
-                    for (int qq = 0; qq < 4; ++qq) {
-                        bool ok;
-                        int lg;
-                        const int64_t ti = tick_of(16 * qq + col, ok, lg);
-                        xs0[qq] = args.tk.s1n[ti];
-                        xs1[qq] = args.tk.s2n[ti];
-                    }
+                    M::load_signals(
+                        args.tk, col,
+                        [&](int smp) {
+                            bool ok;
+                            int lg;
+                            return tick_of(smp, ok, lg);
+                        },
+                        xs0, xs1);
                     bool valid;
                     int lg;
-                    const int64_t tix = tick_of(lane, valid, lg);
-                    const double tmid = args.tk.mid_next[tix], task = args.tk.best_ask[tix], tbid = args.tk.best_bid[tix];
-                    const double tbmax = args.tk.buy_max[tix], tsmin = args.tk.sell_min[tix];
-                    const float x2 = (float)((double)(inv_min + si) / 2.0);
+                    const TickPrices px = load_prices(args.tk, tick_of(lane, valid, lg));
                     float h1[KS][4];
-#pragma unroll
-                    for (int i = 0; i < KS; ++i) {
-                        const int k = 4 * i + grp;
-                        const float a0 = gsm[L::W1 + 3 * k], a1 = gsm[L::W1 + 3 * k + 1], bb = gsm[L::B1 + k];
-                        const float w1s = gsm[L::W1 + 3 * k + 2];
-#pragma unroll
-                        for (int qq = 0; qq < 4; ++qq)
-                            h1[i][qq] = relu(__builtin_fmaf(w1s, x2, __builtin_fmaf(a1, xs1[qq], __builtin_fmaf(a0, xs0[qq], bb))));
-                    }
+                    M::layer1(gsm, grp, xs0, xs1, (float)((double)(inv_min + si) / 2.0), h1);
                     f32x4 acc[4][NT];
-#pragma unroll
-                    for (int i = 0; i < KS; ++i)
-#pragma unroll
-                        for (int qq = 0; qq < 4; ++qq)
-#pragma unroll
-                            for (int rt = 0; rt < NT; ++rt)
-                                acc[qq][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w2f[rt][i], h1[i][qq],
-                                                                                   i == 0 ? b2c[rt] : acc[qq][rt], 0, 0, 0);
+                    M::layer2(w2f, b2c, h1, acc);
                     float* hb = hb_s[si];
-#pragma unroll
-                    for (int qq = 0; qq < 4; ++qq)
-#pragma unroll
-                        for (int rt = 0; rt < NT; ++rt) {
-                            f32x4 v;
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) v[r] = relu(acc[qq][rt][r]);
-                            *reinterpret_cast<f32x4*>(&hb[(16 * qq + col) * HP + 16 * rt + 4 * grp]) = v;
-                        }
+                    M::transpose(acc, hb, grp, col);
                     float o0 = gsm[L::B3], o1 = gsm[L::B3 + 1];
-#pragma unroll
-                    for (int j4 = 0; j4 < H / 4; ++j4) {
-                        const f32x4 h = *reinterpret_cast<const f32x4*>(&hb[lane * HP + 4 * j4]);
-#pragma unroll
-                        for (int r2 = 0; r2 < 2; ++r2) {
-                            const f32x4 w = *reinterpret_cast<const f32x4*>(&w3i[2 * (4 * j4 + 2 * r2)]);
-                            o0 = __builtin_fmaf(w[0], h[2 * r2], o0);
-                            o1 = __builtin_fmaf(w[1], h[2 * r2], o1);
-                            o0 = __builtin_fmaf(w[2], h[2 * r2 + 1], o0);
-                            o1 = __builtin_fmaf(w[3], h[2 * r2 + 1], o1);
-                        }
-                    }
-                    const int32_t oa = act_to_int(rintf(o0 * p.act_scale));  // drl_engine.py:38-39
-                    const int32_t ob = act_to_int(rintf(o1 * p.act_scale));
-                    const StepOut so1 = ftp_step(p, inv_min + si, oa, ob, tmid, task, tbid, tbmax, tsmin);
-                    to_s[si][lane] = (uint8_t)((si + so1.fill_buy - so1.fill_sell) | ((so1.fill_buy | so1.fill_sell) << 7));
+                    M::layer3(hb, w3i, lane, o0, o1);
+                    const StepOut so1 = policy_step(p, inv_min + si, o0, o1, px);
+                    to_s[si][lane] = pack_step(si, so1);
                     rl_s[si][lane] = so1.reward;
                     __syncthreads();
                     if (wv == 0) {
                         // the chunk's steps from K on: segmented map scan, then each tracked
-                        // start's path from its state at K
+                        // start's path from its state at K (own finish: segments of SEG ticks,
+                        // merged into the record the walk left)
                         uint64_t map = kIdentityMap;
                         uint32_t traded = 0;
-                        if (valid) {
-                            for (int st = 0; st < nsi; ++st) {
-                                const uint32_t b8 = to_s[st][lane];
-                                map = (map & ~(0xFFull << (8 * st))) | ((uint64_t)(b8 & 0x7Fu) << (8 * st));
-                                traded |= (b8 >> 7) << st;
-                            }
-                        }
+                        if (valid) unpack_steps(to_s, lane, nsi, map, traded);
                         uint64_t inc = m_scan_seg(map, SEG);
                         uint64_t excl = shfl_up_u64(inc, 1);
                         const int u = lane & (SEG - 1);
@@ -1109,13 +1060,11 @@ int launch_frontier_spill(int hidden, int nsi, unsigned n_waves, int ls, hipStre
     if (!fa.spill_budget || !fa.wspill || n_waves == 0) return SGMM_OK;
     const int total = (int)(n_waves * (unsigned)ls);
     const dim3 grid(kSpillBlocks), block(kWave * nsi);
-    if (hidden == 16) {
-        if (nsi <= 5) SGMM_LAUNCH((k_frontier_spill<16, 5>), grid, block, 0, s, fa, total, ls);
-        else SGMM_LAUNCH((k_frontier_spill<16, 8>), grid, block, 0, s, fa, total, ls);
-    } else {
-        if (nsi <= 5) SGMM_LAUNCH((k_frontier_spill<32, 5>), grid, block, 0, s, fa, total, ls);
-        else SGMM_LAUNCH((k_frontier_spill<32, 8>), grid, block, 0, s, fa, total, ls);
-    }
+    with_int<16, 32>(hidden, [&](auto h) {
+        with_int<5, 8>(nsi <= 5 ? 5 : 8, [&](auto n) {
+            SGMM_LAUNCH((k_frontier_spill<decltype(h)::value, decltype(n)::value>), grid, block, 0, s, fa, total, ls);
+        });
+    });
     SGMM_LAUNCHED();
     return SGMM_OK;
 }
@@ -1126,30 +1075,21 @@ int launch_policy_frontier(int hidden, int nsi, unsigned n_waves, int ls, hipStr
         set_error("fused path scan: one wave per walk, <= %d groups, no spill, hand-off arrays", kFusedMaxGroups);
         return SGMM_ERR_ARG;
     }
-    {
-        const dim3 gs(n_waves * (unsigned)ls);
-#define SGMM_FR_LAUNCH2(H_, N_, SP_)                                                             \
-    do {                                                                                         \
-        if (ls == 4) SGMM_LAUNCH((k_policy_frontier<H_, N_, 4, SP_>), gs, block, 0, s, fa);      \
-        else if (ls == 2) SGMM_LAUNCH((k_policy_frontier<H_, N_, 2, SP_>), gs, block, 0, s, fa); \
-        else SGMM_LAUNCH((k_policy_frontier<H_, N_, 1, SP_>), grid, block, 0, s, fa);            \
-    } while (0)
-#define SGMM_FR_LAUNCH(H_, N_)                                                                  \
-    do {                                                                                        \
-        if (fa.fitness) SGMM_LAUNCH((k_policy_frontier<H_, N_, 1, false, true>), grid, block, 0, s, fa); \
-        else if (fa.spill_budget && fa.wspill) SGMM_FR_LAUNCH2(H_, N_, true);                   \
-        else SGMM_FR_LAUNCH2(H_, N_, false);                                                    \
-    } while (0)
-        if (hidden == 16) {
-            if (nsi <= 5) SGMM_FR_LAUNCH(16, 5);
-            else SGMM_FR_LAUNCH(16, 8);
-        } else {
-            if (nsi <= 5) SGMM_FR_LAUNCH(32, 5);
-            else SGMM_FR_LAUNCH(32, 8);
-        }
-#undef SGMM_FR_LAUNCH
-#undef SGMM_FR_LAUNCH2
-    }
+    with_int<16, 32>(hidden, [&](auto h) {
+        with_int<5, 8>(nsi <= 5 ? 5 : 8, [&](auto n) {
+            constexpr int H = decltype(h)::value, NSI = decltype(n)::value;
+            if (fa.fitness) {  // the fused path scan: one wave per group, no spill
+                SGMM_LAUNCH((k_policy_frontier<H, NSI, 1, false, true>), grid, block, 0, s, fa);
+                return;
+            }
+            with_bool(fa.spill_budget && fa.wspill, [&](auto sp) {
+                with_int<4, 2, 1>(ls, [&](auto l) {
+                    SGMM_LAUNCH((k_policy_frontier<H, NSI, decltype(l)::value, decltype(sp)::value>),
+                                dim3(n_waves * (unsigned)ls), block, 0, s, fa);
+                });
+            });
+        });
+    });
     SGMM_LAUNCHED();
     return SGMM_OK;
 }

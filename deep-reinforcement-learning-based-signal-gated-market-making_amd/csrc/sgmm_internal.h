@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 #include "../../include/sgmm.h"
 #include "sgmm_plan.h"
@@ -70,6 +71,25 @@ struct ProfScope {
 };
 
 inline bool supported_hidden(int h) { return h == 8 || h == 16 || h == 32 || h == 64; }
+
+// Runtime value -> template argument: with_int<16, 32, 64>(hidden, [&](auto h) {
+// ... kernel<decltype(h)::value> ... }) calls f with IntC<V> of the V that equals
+// v (of the last V when none does); with_bool likewise with std::bool_constant.
+template <int N>
+struct IntC {
+    static constexpr int value = N;
+};
+template <int V0, int... Vs, class F>
+inline void with_int(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) f(IntC<V0>{});
+    else if (v == V0) f(IntC<V0>{});
+    else with_int<Vs...>(v, f);
+}
+template <class F>
+inline void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 // Snapshot of the launch-plan overrides (SGMM_PLAN_*, -1 = the default rule):
 // taken once per C-ABI entry, so every launch of the call follows one plan

@@ -1,6 +1,6 @@
 // sgmm_rollout.h -- device layout and helpers shared by the rollout translation
-// units (sgmm_rollout.hip: tables, path scans, host entry points;
-// sgmm_frontier.hip: the frontier kernel).
+// units (sgmm_rollout.hip: path scans, host entry points; sgmm_table.hip: the
+// policy tables; sgmm_frontier.hip: the frontier kernel).
 #pragma once
 
 #include "sgmm_device.h"
@@ -146,10 +146,6 @@ __device__ __forceinline__ uint32_t chunk_base(int64_t step_off, int e) {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-template <int N>
-struct IntC {
-    static constexpr int value = N;
-};
 // number of lanes below this one whose bit is set in m
 __device__ __forceinline__ int mbcnt64(uint64_t m) {
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -305,5 +301,25 @@ int launch_policy_frontier(int hidden, int nsi, unsigned n_waves, int ls, hipStr
 // completes the chunks of the walks that spilled (fa.wspill) tick-parallel; a
 // fixed grid (graph-capturable) that exits at once when no walk spilled
 int launch_frontier_spill(int hidden, int nsi, unsigned n_waves, int ls, hipStream_t s, const FrontierArgs& fa);
+
+// ------------------------------------------------------------------ table launches (sgmm_table.hip)
+// The walk-order feedback's job (walk_reorder_block): rank the populations by
+// the slots their walks just ran and rewrite the walk order
+struct ReorderJob {
+    const uint32_t* wslots;
+    int32_t* order;  // null: no job
+    int32_t n, whole, gtail, pop_eps;
+    uint32_t w_whole = 5, w_split = 4;  // score weights (SGMM_PLAN_REORDER_WEIGHTS for experiments)
+    int32_t len = 0;                    // the episodes' (common) length: groups past the last chunk have no count
+};
+// launches the plan's table (kind: TableValu, TableSp, TableV3 or TableMfma) over
+// n_ep episodes of at most max_len ticks; rj (TableSp; may be null): a walk-order
+// job to run as the state-parallel table's extra workgroup
+void launch_policy_table(PolicyKernel kind, int hidden, bool arl, int nsi, int max_len, int n_ep,
+                         const sgmm_ticks& tk, const EpArrays& ep, const sgmm_env_params* params,
+                         const GenomeSrc& src, int32_t inv_min, uint64_t* ctr, uint64_t* cmaps, uint64_t* fills,
+                         double* rew, const ReorderJob* rj, hipStream_t s);
+// the walk-order job alone (k_walk_reorder)
+void launch_walk_reorder(const ReorderJob& job, hipStream_t s);
 
 }  // namespace sgmm

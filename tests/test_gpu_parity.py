@@ -345,6 +345,41 @@ def test_state_parallel_table(sgmm, oracle, caps, H, plan):
         assert np.array_equal(f, want_f), sp
 
 
+@pytest.mark.parametrize("H,caps,arl", [(64, (3, -4), False), (64, (2, -2), True), (16, (3, -4), True),
+                                        (32, (3, -4), True)],
+                         ids=["h64_nsi8", "h64_adv", "h16_nsi8_adv", "h32_nsi8_adv"])
+def test_mfma_table_states_and_adversary(sgmm, oracle, H, caps, arl, plan):
+    """k_policy_table_mfma where no other test reaches it -- H = 64 with 8
+    inventory values, the adversary at H = 64, the adversary with 8 inventory
+    values at H = 16 / 32 -- against the oracle bit for bit, on ragged lengths
+    (partial last chunk, partial last block of four chunks, zero-length and
+    one-tick episodes)."""
+    from sgmm_amd import synthetic
+    i_max, i_min = caps
+    lens = np.array([0, 1, 63, 64, 65, 257, 700], np.int64)
+    P, T = len(lens), int(lens.max())
+    b = synthetic.bundle_510300(T, seed=7)
+    st = synthetic.train_stats(b)
+    pop = synthetic.population(P, H, sigma=0.3, seed=8)
+    adv = synthetic.population(P, 32, sigma=1.0, seed=9) if arl else None  # adversary genomes: 1250 floats
+    ep_adv = np.arange(P) if arl else None
+    s1n, s2n = sgmm.normalize_signals(b[0], b[1], st)
+    ticks = sgmm.TickStore()
+    seg = ticks.add(b, st)
+    ticks.to(DEV)
+    params = sgmm.params_tensor([sgmm.EnvConfig(phi=0.0001, tick_size=0.001, i_max=i_max, i_min=i_min)], DEV)
+    eb = sgmm.EpisodeBatch(np.arange(P), np.full(P, ticks.segments[seg][0]), lens, np.zeros(P), adv=ep_adv,
+                           inv_min=i_min, inv_max=i_max).to(DEV)
+    plan(policy_path="table")
+    fit, trd = sgmm.RolloutEngine(DEV).fitness(ticks, eb, params, pop.to(DEV), H, adv.to(DEV) if arl else None)
+    want_f, want_t = oracle.evaluate_batch(pop.numpy(), H, adv.numpy() if arl else None, (s1n, s2n) + tuple(b[2:]),
+                                           np.arange(P), ep_adv, np.zeros(P), lens, np.zeros(P),
+                                           [oracle.params(phi=0.0001, tick=0.001, i_max=i_max, i_min=i_min)],
+                                           n_threads=8)
+    assert np.array_equal(trd.cpu().numpy(), want_t)
+    assert np.array_equal(fit.cpu().numpy(), want_f)
+
+
 def _seq_sum(init, x):
     s = np.float64(init)
     for v in np.asarray(x, np.float64):
