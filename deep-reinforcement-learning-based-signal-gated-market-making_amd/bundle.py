@@ -98,7 +98,8 @@ class EventBarsGPU:
         X = torch.zeros((max(int(win_off[-1]), 1), TIME_STEPS), dtype=torch.float32, device=dev)
         y = torch.zeros(max(int(win_off[-1]), 1), dtype=torch.float32, device=dev)
         nw = torch.zeros(max(self.n_days, 1), dtype=torch.int32, device=dev)
-        bars_max = int((self.n_events.max() if self.n_days else 0) // EVENT_STEP + 1)
+        # len(range(0, n - 19, 19)) of the longest day, the kernel's own bar count
+        bars_max = int(max((int(self.n_events.max()) if self.n_days else 0) - 1, 0) // EVENT_STEP)
         win_off_d = torch.from_numpy(win_off).to(dev)  # held until the launch is enqueued
         check(self.L.sgmm_bar_windows(ctypes.byref(self.bars), self.n_days, ptr(self._in["snap_off"]),
                                       ptr(win_off_d), ptr(X), ptr(y), ptr(nw),

@@ -13,9 +13,10 @@
 //                the events.
 //   bar mids     loaders/HFTLoader.py:141-169 (SGU2DataPro): per 19-event
 //                group 0.5*(max p_buy_max + min p_sell_min) with the pandas
-//                mean fallbacks (numpy pairwise sum / 19), ffill, float32,
-//                floor 1e-5, returns (m - m_lag)/(m_lag + 1e-9), 10-step
-//                windows, nan_to_num.
+//                mean fallbacks (Series.mean skips NaN quotes: numpy pairwise
+//                sum with NaN as 0 / count of non-NaN, NaN when none), ffill,
+//                float32, floor 1e-5, returns (m - m_lag)/(m_lag + 1e-9),
+//                10-step windows, nan_to_num.
 //   step bundle  pipeline/agent_trainer.py:45-78: for the last n sampled
 //                events (every 19th), the window max/min of the traded
 //                extremes over the inclusive .loc range between consecutive
@@ -151,19 +152,33 @@ __global__ __launch_bounds__(kDayBlock) void k_event_bars(sgmm_day_streams in, s
     if (tid == 0) out.n_events[d] = ne;
 }
 
-// numpy's float64 add.reduce order for n in [8, 128): 8 strided accumulators,
-// combined pairwise, then the tail in order
-__device__ double pairwise_sum_19(const double* a) {
+constexpr int kEventStep = 19, kTimeSteps = 10;
+constexpr int kMaxBars = 4096;  // bars per day held in LDS (4096 * 19 events)
+
+// pandas' Series.mean of 19 quotes (nanops.nanmean, skipna): NaN counts as 0
+// in numpy's float64 add.reduce order for n in [8, 128) -- 8 strided
+// accumulators, combined pairwise, then the tail in order -- and the sum is
+// divided by the number of non-NaN quotes; NaN when there is none.  A call,
+// not inlined: with both means inlined k_bar_windows holds 38 quotes at once
+// and spills at the 128 VGPRs a 1024-thread block leaves it (66 and none so)
+__device__ __noinline__ double skipna_mean_19(const double* a) {
+    int count = 0;
+    auto q = [&](int j) -> double {
+        const double x = a[j];
+        const bool ok = x == x;
+        count += ok ? 1 : 0;
+        return ok ? x : 0.0;
+    };
     double r[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
+    for (int j = 0; j < 8; ++j) r[j] = q(j);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = r[j] + a[8 + j];
+    for (int j = 0; j < 8; ++j) r[j] = r[j] + q(8 + j);
     double s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    s = s + a[16];
-    s = s + a[17];
-    s = s + a[18];
-    return s;
+    s = s + q(16);
+    s = s + q(17);
+    s = s + q(18);
+    return count > 0 ? s / count : NAN;
 }
 
 __device__ __forceinline__ double nan_max_run(const double* a, int n) {
@@ -179,9 +194,6 @@ __device__ __forceinline__ double nan_min_run(const double* a, int n) {
         if (a[i] == a[i]) m = (m != m || a[i] < m) ? a[i] : m;
     return m;
 }
-
-constexpr int kEventStep = 19, kTimeSteps = 10;
-constexpr int kMaxBars = 4096;  // bars per day held in LDS (4096 * 19 events)
 
 // SGU2DataPro.gen_dataset (HFTLoader.py:139-169) per day: X[w][k] = return
 // k of window w (float32), y[w]; n_windows[d] = max(0, bars - 11)
@@ -203,8 +215,8 @@ __global__ __launch_bounds__(kDayBlock) void k_bar_windows(sgmm_event_bars ev, c
         const int64_t a = e0 + (int64_t)g * kEventStep;
         const double bmax = nan_max_run(ev.p_buy_max + a, kEventStep);
         const double smin = nan_min_run(ev.p_sell_min + a, kEventStep);
-        const double am = pairwise_sum_19(ev.ask + a) / kEventStep;
-        const double bm = pairwise_sum_19(ev.bid + a) / kEventStep;
+        const double am = skipna_mean_19(ev.ask + a);
+        const double bm = skipna_mean_19(ev.bid + a);
         double v;
         if (bmax == bmax && smin == smin) v = 0.5 * (bmax + smin);
         else if (smin == smin) v = 0.5 * (am + smin);
@@ -239,6 +251,9 @@ __global__ __launch_bounds__(kDayBlock) void k_bar_windows(sgmm_event_bars ev, c
     __syncthreads();
     const int nr = nb - 1, nw = nr - kTimeSteps;
     const int64_t w0 = win_off[d];
+    // nan_to_num: a return is +inf when a float32-infinite bar follows a finite
+    // one.  The -FLT_MAX arm mirrors nan_to_num but cannot be reached: the floor
+    // keeps lag >= 1e-5 and turns cur = -inf into 1e-5, so no return is -inf.
     for (int idx = tid; idx < nw * kTimeSteps; idx += kDayBlock) {
         const int w = idx / kTimeSteps, k = idx % kTimeSteps;
         const float v = ret[w + k];

@@ -11,14 +11,16 @@ Restated (numpy, plain loops where order matters), with the reference lines:
                merge_asof(direction='backward') onto the events
   bar_mids     loaders/HFTLoader.py:141-156  per 19-event group:
                0.5*(max p_buy_max + min p_sell_min) with the mean-price
-               fallbacks; pandas Series.mean == numpy pairwise sum / count
+               fallbacks; pandas Series.mean skips NaN: numpy pairwise sum
+               with NaN as 0 / count of non-NaN quotes (skipna_mean)
   sgu2_windows loaders/HFTLoader.py:158-169  ffill, float32, floor 1e-5,
                (m - m_lag) / (m_lag + 1e-9), 10-step windows, nan_to_num
   step_bundle  pipeline/agent_trainer.py:45-78  alignment to the signals,
                inclusive .loc window max/min, ask/bid now, mid at the next step
 
 Pinned by tests/golden/g6_bundle.npz (the reference run on synthetic days,
-tests/golden/gen_golden_bundle.py).
+tests/golden/gen_golden_bundle.py) and tests/golden/g11_bundle_edges.npz (days
+with NaN quotes and non-positive trade prices, gen_golden_bundle_edges.py).
 """
 from __future__ import annotations
 
@@ -117,6 +119,18 @@ def event_bars(snap: dict, tick: dict) -> dict:
     return out
 
 
+def skipna_mean(a) -> float:
+    """pandas' Series.mean (nanops.nanmean, skipna): NaN replaced by 0 in the
+    same pairwise sum, divided by the count of non-NaN values; NaN when that
+    count is 0."""
+    a = np.asarray(a, np.float64)
+    nan = np.isnan(a)
+    count = int(len(a) - nan.sum())
+    if count == 0:
+        return np.float64(np.nan)
+    return pairwise_sum(np.where(nan, 0.0, a)) / count
+
+
 def bar_mids(ev: dict, event_step: int = 19) -> np.ndarray:
     """SGU2DataPro's per-group mid estimate m (HFTLoader.py:141-156)."""
     n = len(ev["trade_time"])
@@ -124,8 +138,8 @@ def bar_mids(ev: dict, event_step: int = 19) -> np.ndarray:
     for i in range(0, n - event_step, event_step):
         sl = slice(i, i + event_step)
         bmax, smin = nanmax(ev["p_buy_max"][sl]), nanmin(ev["p_sell_min"][sl])
-        a_mean = pairwise_sum(ev["askprice1"][sl]) / event_step
-        b_mean = pairwise_sum(ev["bidprice1"][sl]) / event_step
+        a_mean = skipna_mean(ev["askprice1"][sl])
+        b_mean = skipna_mean(ev["bidprice1"][sl])
         if not np.isnan(bmax) and not np.isnan(smin):
             m.append(0.5 * (bmax + smin))
         elif np.isnan(bmax) and not np.isnan(smin):
