@@ -25,8 +25,16 @@ namespace sgmm {
 // pattern: while another wave of the SIMD streams MFMAs, integer VALU ops
 // issue at half rate and float ops at full rate (tools/mb/mb_mfma_xwave2.hip).
 // Equals torch's relu for every non-NaN input (-0.0 -> +0.0 up to the sign of
-// an exact zero, which no action depends on); NaN pre-activations (NaN state
-// inputs only) are outside the parity domain (oracle/sgmm_oracle.c relu32).
+// an exact zero, which no action depends on), subnormals kept (the library is
+// built without denormal flushing; tests/test_gpu_value_domain.py's sub_*
+// regimes pin that on every policy kernel).  A NaN pre-activation -- from a
+// NaN state input, or from finite weights once an activation overflowed to
+// inf and meets weights of both signs in the next chain (inf - inf) --
+// contributes +0 whatever its sign (med3 with a NaN operand returns min3, and
+// min drops the NaN; measured, same test), as oracle/sgmm_oracle.c relu32
+// does; torch's relu propagates the NaN instead.  The other departure from the
+// reference at the value edge: act_to_int saturates at int32 where the
+// reference's int64 action does not (beyond |raw * 5| = 2^31).
 __device__ __forceinline__ float relu(float a) {
 #ifdef SGMM_RELU_INT  // A/B builds only: round 1's integer max on the bit pattern
     return __int_as_float(max(__float_as_int(a), 0));
@@ -40,10 +48,12 @@ __device__ __forceinline__ float relu(float a) {
 // float -> int action: saturating, NaN -> INT32_MIN (the x86 cvtt value numpy's
 // astype(int) produces).  Values are already integral (rint) when called.
 // Branch-free: fmaxf maps NaN to the lower clamp, so NaN and -inf both land
-// on -2^31; the upper clamp is the largest float below 2^31.
+// on -2^31; the upper clamp is the largest float below 2^31, which is an int32
+// value itself and converts as such (the reference's int64 action there is
+// 2147483520); only floats above it saturate to INT32_MAX.
 __device__ __forceinline__ int32_t act_to_int(float r) {
     const int32_t v = (int32_t)fminf(fmaxf(r, -2147483648.0f), 2147483520.0f);
-    return r >= 2147483520.0f ? INT32_MAX : v;
+    return r > 2147483520.0f ? INT32_MAX : v;
 }
 
 // ---------------------------------------------------------------- FTPEnv.step
@@ -55,14 +65,18 @@ struct StepOut {
 };
 
 // One FTPEnv.step from inventory `inv` with final offsets (adversary already
-// added, market_env.py:25-28).  Pure function of its inputs.
+// added, market_env.py:25-28).  Pure function of its inputs.  The offsets are
+// doubles: the reference adds the adversary's delta to the action in int64
+// (market_env.py:26-28) and multiplies that sum by the tick, and
+// (double)oa + (double)da is that sum exactly (both are int32), where an int32
+// oa + da wraps once the action has saturated (tests/golden/g12_int_edges.npz).
 __device__ __forceinline__ StepOut ftp_step(const sgmm_env_params& p, int32_t inv,
-                                            int32_t off_a, int32_t off_b, double mid_next,
+                                            double off_a, double off_b, double mid_next,
                                             double best_ask, double best_bid, double buy_max,
                                             double sell_min) {
     StepOut o;
-    const double qa = best_ask + (double)off_a * p.tick;   // market_env.py:30
-    const double qb = best_bid - (double)off_b * p.tick;   // market_env.py:31
+    const double qa = best_ask + off_a * p.tick;           // market_env.py:30
+    const double qb = best_bid - off_b * p.tick;           // market_env.py:31
     o.fill_buy = (inv < p.i_max) && (qb >= sell_min);      // :34,:37 (NaN -> no fill)
     o.fill_sell = (inv > p.i_min) && (qa <= buy_max);      // :35,:38
     // both sides computed, then selected: the same operations in the same
@@ -80,6 +94,16 @@ __device__ __forceinline__ StepOut ftp_step(const sgmm_env_params& p, int32_t in
     o.fee_paid = fees;
     o.reward = pnl - p.phi * (double)(q < 0 ? -q : q);     // :57-58
     return o;
+}
+
+// ... with the action alone (no adversary): (double)off is the same conversion
+// the int32 form always made.
+__device__ __forceinline__ StepOut ftp_step(const sgmm_env_params& p, int32_t inv,
+                                            int32_t off_a, int32_t off_b, double mid_next,
+                                            double best_ask, double best_bid, double buy_max,
+                                            double sell_min) {
+    return ftp_step(p, inv, (double)off_a, (double)off_b, mid_next, best_ask, best_bid, buy_max,
+                    sell_min);
 }
 
 // cash update with the reference's two separate in-place ops (:47, :53)

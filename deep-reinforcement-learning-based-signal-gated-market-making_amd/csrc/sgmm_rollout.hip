@@ -1296,8 +1296,9 @@ __global__ __launch_bounds__(kWave) void k_rollout_direct(
             da = lut[0][s];
             db = lut[1][s];
         }
-        const StepOut st = ftp_step(p, inv, oa + da, ob + db, tk.mid_next[ti], tk.best_ask[ti],
-                                    tk.best_bid[ti], tk.buy_max[ti], tk.sell_min[ti]);
+        const StepOut st = ftp_step(p, inv, (double)oa + (double)da, (double)ob + (double)db,
+                                    tk.mid_next[ti], tk.best_ask[ti], tk.best_bid[ti], tk.buy_max[ti],
+                                    tk.sell_min[ti]);
         cash = apply_cash(cash, st);
         inv = st.inv;
         total += st.reward;
@@ -1367,10 +1368,10 @@ __global__ void k_env_step(const sgmm_env_params* __restrict__ params,
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const sgmm_env_params p = params[pidx ? pidx[i] : 0];
-    int32_t oa = action[2 * i], ob = action[2 * i + 1];
-    if (adv_action) {  // market_env.py:25-28
-        oa += adv_action[2 * i];
-        ob += adv_action[2 * i + 1];
+    double oa = (double)action[2 * i], ob = (double)action[2 * i + 1];
+    if (adv_action) {  // market_env.py:25-28 (the int64 sum, exact in float64)
+        oa += (double)adv_action[2 * i];
+        ob += (double)adv_action[2 * i + 1];
     }
     const StepOut so = ftp_step(p, inventory[i], oa, ob, mid[i], ask[i], bid[i], bmax[i], smin[i]);
     inventory[i] = so.inv;

@@ -94,8 +94,8 @@ __global__ __launch_bounds__(kChunk * 8) void k_policy_table(
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const int s = 4 * w + c;
-                const StepOut so = ftp_step(p, inv, oa + lut[0][s], ob + lut[1][s], mid, ask,
-                                            bid, bmax, smin);
+                const StepOut so = ftp_step(p, inv, (double)oa + (double)lut[0][s],
+                                            (double)ob + (double)lut[1][s], mid, ask, bid, bmax, smin);
                 code[s][lane] = (uint8_t)(so.fill_buy | (so.fill_sell << 1));
                 rew[s * ep.rs + row] = so.reward;  // per-state planes (SoA): coalesced rows
             }
@@ -340,7 +340,8 @@ __global__ __launch_bounds__(kWave * 4, H <= 16 ? 5 : ((ARL && H <= 32) ? 3 : 1)
                     for (int c2 = c - 1; c2 >= 0; --c2)
                         if (dac[c2] == dac[c] && dbc[c2] == dbc[c]) dup = c2;
                     if (dup < 0) {
-                        const StepOut so = ftp_step(p, inv, oa + dac[c], ob + dbc[c], px.mid, px.ask, px.bid,
+                        const StepOut so = ftp_step(p, inv, (double)oa + (double)dac[c],
+                                                    (double)ob + (double)dbc[c], px.mid, px.ask, px.bid,
                                                     px.bmax, px.smin);
                         rc[c] = so.reward;
                         fc[c] = so.fill_buy | (so.fill_sell << 1);

@@ -57,28 +57,40 @@ typedef struct {
     float   *raw_a, *raw_b;       /* raw MLP outputs */
 } orc_trace;
 
-/* float -> int conversion used for actions: saturating, NaN -> INT32_MIN
- * (x86 cvtt semantics, which is what numpy's astype(int) yields for NaN). */
+/* float -> int conversion used for actions: the reference's int64 action
+ * (numpy's astype(int)) saturated at int32, NaN -> INT32_MIN.  2147483520 =
+ * 2^31 - 128, the largest float below 2^31, is itself an int32 value and
+ * converts as such (tests/golden/g12_int_edges.npz big_raw). */
 static int32_t act_to_int(float r)
 {
     if (r != r) return INT32_MIN;
-    if (r >= 2147483520.0f) return INT32_MAX;
+    if (r > 2147483520.0f) return INT32_MAX;
     if (r <= -2147483648.0f) return INT32_MIN;
     return (int32_t)r;
 }
 
-/* ReLU on the bit pattern, max(bits, 0) as int32.  The kernels use
- * v_med3_f32(a, 0, +inf) instead (sgmm_device.h relu); the two agree for every
- * non-NaN input except the sign of a zero (-0.0 -> +0.0 here, -0.0 or +0.0
- * there), which changes no dot product's value beyond the sign of an exact
- * zero and so no action.  Both equal torch's relu on non-NaN inputs; NaN
- * pre-activations (only NaN state inputs produce them) are outside the
- * parity domain, where the two forms may differ. */
+/* ReLU on the bit pattern: the patterns 0x00000001 .. 0x7F800000 (positive
+ * subnormals up to +inf) pass, everything else -- zeros, negatives and EVERY
+ * NaN, whatever its sign -- gives +0.  The kernels use v_med3_f32(a, 0, +inf)
+ * instead (sgmm_device.h relu); the two agree for every input except the sign
+ * of a zero (-0.0 -> +0.0 here, -0.0 or +0.0 there), which changes no dot
+ * product's value beyond the sign of an exact zero and so no action.  Both
+ * equal torch's relu on non-NaN inputs and keep subnormals.
+ *
+ * The port's rule for a NaN pre-activation is that it contributes 0 (measured
+ * on gfx950 for NaNs of both signs, tests/test_gpu_value_domain.py); torch's
+ * relu propagates it instead.  NaN pre-activations come from NaN state inputs
+ * and from finite weights alike: an activation that overflowed to inf meets
+ * weights of both signs in the next chain, inf - inf (the ovf_l1 regime of
+ * tests/value_regimes.py; a chain over finite activations reaches +-inf but
+ * never NaN, the fma's product being exact).  A plain max(bits, 0) would zero
+ * only negative NaNs -- the default NaN of x86, not np.nan and not every
+ * host's.  Branch-free: one unsigned compare and a mask. */
 static float relu32(float a)
 {
-    int32_t b;
+    uint32_t b;
     memcpy(&b, &a, sizeof b);
-    b = b > 0 ? b : 0;
+    b &= (uint32_t)0 - (uint32_t)(b - 1u < 0x7F800000u);
     memcpy(&a, &b, sizeof a);
     return a;
 }
@@ -90,9 +102,13 @@ int orc_env_step(const orc_params *p, int32_t *inv, double *cash,
                  double mid_next, double best_ask, double best_bid,
                  double buy_max, double sell_min, double *out4, int32_t *fills)
 {
-    if (has_adv) { off_a += adv_a; off_b += adv_b; }          /* market_env.py:25-28 */
-    const double quote_ask = best_ask + (double)off_a * p->tick;  /* :30 */
-    const double quote_bid = best_bid - (double)off_b * p->tick;  /* :31 */
+    /* market_env.py:25-28 adds the delta in int64 (actions are astype(int)); an
+     * int32 sum overflows once the action has saturated (g12_int_edges).  The
+     * kernels add the two as doubles, which is the same sum exactly. */
+    int64_t sa = off_a, sb = off_b;
+    if (has_adv) { sa += adv_a; sb += adv_b; }
+    const double quote_ask = best_ask + (double)sa * p->tick;     /* :30 */
+    const double quote_bid = best_bid - (double)sb * p->tick;     /* :31 */
     const int32_t pos = *inv;
     const int buy = (pos < p->i_max) && (quote_bid >= sell_min);   /* :34,37 */
     const int sell = (pos > p->i_min) && (quote_ask <= buy_max);   /* :35,38 */
