@@ -112,7 +112,16 @@ class MBBResult(ctypes.Structure):
         [(n, ctypes.c_int32) for n in ("n_returns", "num_blocks", "zero_replicates", "flags")]
 
 
+class Sgu2Task(ctypes.Structure):
+    """sgmm_sgu2_task: one SGU2 fit (device pointers, see include/sgmm.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("X_train", "y_train", "X_val", "y_val", "weights", "best_weights",
+                                               "perm", "keep", "train_loss", "val_loss", "epochs_run",
+                                               "best_epoch")] + \
+        [("n", ctypes.c_int64), ("nv", ctypes.c_int64), ("seed", ctypes.c_uint64), ("lr", ctypes.c_double)]
+
+
 assert ctypes.sizeof(EnvParams) == 48
+assert ctypes.sizeof(Sgu2Task) == 128
 assert ctypes.sizeof(DMResult) == 40
 assert ctypes.sizeof(MBBResult) == 40
 assert ctypes.sizeof(QuoteRule) == 144
@@ -177,6 +186,12 @@ SIGNATURES = {
                                              ctypes.c_size_t, _VP]),
     "sgmm_bar_windows": (ctypes.c_int, [ctypes.POINTER(EventBars), _I32, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
     "sgmm_sgu2_forward": (ctypes.c_int, [_VP, _I32, _VP, _I64, _I32, _VP, _VP, _VP, _VP]),
+    "sgmm_sgu2_train_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
+    "sgmm_sgu2_train": (ctypes.c_int, [_VP, ctypes.POINTER(Sgu2Task), _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP,
+                                       ctypes.c_float, _VP, _SZ, _VP]),
+    "sgmm_sgu2_loss_grad": (ctypes.c_int, [_VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP, ctypes.c_float, _VP, _VP,
+                                           _VP, _SZ, _VP]),
+    "sgmm_sgu2_schedule": (ctypes.c_int, [_U64, _I64, _I32, _I32, _VP, _VP, _VP]),
     "sgmm_step_bundle": (ctypes.c_int, [ctypes.POINTER(EventBars), _I32, _VP, _VP, _VP, _I32, _VP, _VP, _VP,
                                         _VP, _VP, _VP]),
     "sgmm_plan_set": (ctypes.c_int, [_I32, _I32]),

@@ -22,25 +22,12 @@
 // LSTM within the tolerance tests/test_sgu2.py states.
 #include <cmath>
 
-#include "sgmm_device.h"
 #include "sgmm_internal.h"
+#include "sgmm_sgu2_device.h"
 
 namespace sgmm {
 
 constexpr int kSgu2Block = 256;
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-// constant address space: wave-uniform loads through it become s_load
-typedef const __attribute__((address_space(4))) float* CFloatPtr;
-constexpr float kLog2e = 1.4426950408889634f;
-
-__device__ __forceinline__ float sigmoid_fast(float x) {
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-x * kLog2e));
-}
-
-__device__ __forceinline__ float tanh_fast(float x) {
-    return fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.0f * kLog2e * x)), 1.0f);
-}
 
 template <int H>
 __global__ __launch_bounds__(kSgu2Block) void k_sgu2(const float* __restrict__ w, const float* __restrict__ X,

@@ -678,6 +678,92 @@ int sgmm_sgu2_forward(const float *weights, int32_t hidden, const float *X, int6
                       void *stream);
 
 /* ------------------------------------------------------------------------
+ * SGU2 training (models/GateUnits.py:66-114 driven by
+ * pipeline/sgu_trainer.py:91-112): whole fits in one launch, one workgroup
+ * per fit.  Weights and Adam moments stay in LDS for the whole fit; every
+ * epoch, minibatch, the validation pass, early stopping and the history run
+ * on the device.  Fits are independent: K fits in one launch equal K launches
+ * of one fit bit for bit, and the same inputs give the same bits on every run.
+ *
+ * Per minibatch: SGU2Model.forward in train mode (the sgmm_sgu2_forward
+ * recurrence in its operation order, with a tanh that is accurate relative to
+ * small arguments too, since the gradients are products with h; then
+ * h_T * keep * 5 -- Dropout(0.8) -- then fc), MSE with the
+ * mean over the minibatch, full BPTT in float32 and one torch.optim.Adam step
+ * (defaults: betas 0.9 / 0.999, eps 1e-8; bias corrections in float64).  A
+ * minibatch of more than 256 samples is walked in chunks of 256.  The last
+ * minibatch of an epoch may be partial (drop_last=False).  Per epoch: eval
+ * forward over the validation windows, train_loss[e] = sum of the minibatch
+ * losses / number of minibatches, val_loss[e] = MSE (NaN when nv == 0); an
+ * improvement is val_loss < best (strict, so NaN never improves); the fit stops
+ * when `patience` epochs in a row did not improve (GateUnits.py:101-109).
+ *
+ * Schedule: the sample at position i of epoch e and the keep mask of its
+ * hidden unit j.  Given explicitly (perm / keep), or generated from `seed`
+ * with Philox4x32-10 (key = seed low word, seed high word):
+ *   keep(e, i, j) = word (j & 3) of counter (j >> 2, i, e, 4) < 858993459
+ *                   (= floor(0.2 * 2^32): keep with probability 0.2);
+ *   perm(e, i): with b = max(2, bit length of n - 1), a = b / 2, c = b - a,
+ *     x -> F(x): six rounds r = 0..5 of { L = x >> c; R = x & (2^c - 1);
+ *     L ^= word 0 of counter (R, r, e, 3) & (2^a - 1); x = (R << a) | L },
+ *     a bijection of [0, 2^b); perm = F applied to i until the value is < n
+ *     (cycle walking: an exact permutation of [0, n)).
+ * Stream ids 3 and 4 do not collide with the GA's (0, 1) or the bootstrap's (2).
+ * ------------------------------------------------------------------------ */
+typedef struct sgmm_sgu2_task {
+    const float   *X_train;      /* [n, time_steps] windows */
+    const float   *y_train;      /* [n] labels */
+    const float   *X_val;        /* [nv, time_steps]; may be NULL when nv == 0 */
+    const float   *y_val;        /* [nv] */
+    float         *weights;      /* [P] sgmm_sgu2_forward layout: initial in, final out */
+    float         *best_weights; /* [P] or NULL: the weights after the best epoch
+                                    (written at each improvement; untouched if none) */
+    const int32_t *perm;         /* [epochs, n] or NULL (Philox) */
+    const uint8_t *keep;         /* [epochs, n, hidden] 0 / 1, or NULL (Philox) */
+    double        *train_loss;   /* [epochs]; rows >= epochs_run are not written */
+    double        *val_loss;     /* [epochs] */
+    int32_t       *epochs_run;   /* [1] */
+    int32_t       *best_epoch;   /* [1]; -1 when no epoch improved */
+    int64_t        n;            /* training windows, 1 .. 2^31 - 1 */
+    int64_t        nv;           /* validation windows, >= 0 */
+    uint64_t       seed;         /* Philox key of the generated schedule */
+    double         lr;           /* Adam learning rate */
+} sgmm_sgu2_task;                /* 128 bytes */
+
+/* Bytes of workspace for n_tasks fits (per fit: 256 samples x time_steps x
+ * (6 hidden + 1) float32 activations for the backward pass).  A pure function
+ * of its arguments; 0 for unsupported arguments. */
+size_t sgmm_sgu2_train_workspace_bytes(int32_t hidden, int32_t time_steps, int32_t n_tasks);
+
+/* n_tasks fits in one launch.  tasks: DEVICE array of records whose members
+ * point to device memory; tasks_host: the HOST copy of the same records, read
+ * for the argument checks (as rules_host of sgmm_rollout_summary).  mean / std:
+ * the float32 StandardScaler3D fit applied to train and validation windows in
+ * the kernel, or both NULL.  Labels are multiplied by label_scale
+ * (sgu_trainer.py:55).  batch in 1..1024, epochs >= 0, patience >= 1,
+ * time_steps >= 1, hidden in {10, 16, 32}. */
+int sgmm_sgu2_train(const sgmm_sgu2_task *tasks, const sgmm_sgu2_task *tasks_host, int32_t n_tasks,
+                    int32_t hidden, int32_t time_steps, int32_t batch, int32_t epochs, int32_t patience,
+                    const float *mean, const float *std, float label_scale, void *workspace,
+                    size_t workspace_bytes, void *stream);
+
+/* One minibatch of the trainer's device code: X[n, time_steps], y[n], n in
+ * 1..1024 -> loss[1] (MSE, mean over n) and its gradient grad[P] in the weight
+ * layout.  keep: [n, hidden] 0 / 1 (train mode: h_T * keep * 5) or NULL (eval
+ * mode, no dropout).  workspace: sgmm_sgu2_train_workspace_bytes(hidden,
+ * time_steps, 1) bytes. */
+int sgmm_sgu2_loss_grad(const float *weights, int32_t hidden, const float *X, const float *y, int32_t n,
+                        int32_t time_steps, const uint8_t *keep, const float *mean, const float *std,
+                        float label_scale, float *loss, float *grad, void *workspace,
+                        size_t workspace_bytes, void *stream);
+
+/* The schedule `seed` yields: perm[epochs, n] and keep[epochs, n, hidden]
+ * (either may be NULL).  Passed back as a task's explicit schedule they
+ * reproduce the Philox run bit for bit. */
+int sgmm_sgu2_schedule(uint64_t seed, int64_t n, int32_t hidden, int32_t epochs, int32_t *perm,
+                       uint8_t *keep, void *stream);
+
+/* ------------------------------------------------------------------------
  * Launch-plan overrides (ABI 5), for tests and A/B experiments.  The shipped
  * library reads no environment variable; its launch plan (policy kernel,
  * chunk groups, lane split, scan width, spill budget) follows the measured
