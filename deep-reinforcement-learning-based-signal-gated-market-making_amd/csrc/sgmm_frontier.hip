@@ -3,12 +3,14 @@
 // Reference semantics: evaluate_individual (Env/drl_engine.py:9-67) over a GA
 // population -- per tick the TradingPolicy forward (models/model.py:5-26) and
 // FTPEnv.step (Env/market_env.py:22-67) -- for the inventory states a chunk's
-// paths occupy; the path scan (sgmm_rollout.hip) sums the rewards.
+// paths occupy; the path scan (sgmm_scan.hip, or the walk itself: fused_scan
+// below, from the same pieces, sgmm_scan.h) sums the rewards.
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
 
 #include "sgmm_mlp_mfma.h"  // the spill kernel's MLP (with sgmm_rollout.h)
+#include "sgmm_scan.h"      // the fused scan's pieces
 
 namespace sgmm {
 
@@ -21,8 +23,9 @@ __device__ unsigned int g_thwid[kStampWaves][2];  // HW_ID, XCC_ID of each wave
 
 // ------------------------------------------------------------------ fused path scan
 // k_policy_frontier<..., FS = true>: the walks sum their own episode while the
-// launch's longer walks still run -- the path scan's frontier path (sgmm_rollout.hip,
-// scan_episode<..., FR = true>) for one wave and one chunk group at a time: the
+// launch's longer walks still run -- the path scan's frontier path (sgmm_scan.hip,
+// scan_episode<..., FR = true>; the pieces of sgmm_scan.h with the write-through
+// loader SharedLd) for one wave and one chunk group at a time: the
 // group's chunk start states from its composed chunk maps and the state the
 // episode's path enters it in, the trades along that path, then the rewards of the
 // path added in windows of kFusedWin ticks as the plain sequential float64 chain
@@ -43,19 +46,6 @@ struct FusedChain {
     uint32_t st;  // the state the path enters the next chunk in (0 .. nsi - 1)
     int32_t tr;   // trades so far
 };
-// global loads of handed-over bytes: write-through (sc1) both ways
-// (MI355X_MICROARCH.md, inter-workgroup visibility, row 1)
-// (a wave's own bytes too: its stores drained first, one code path for both)
-template <class T>
-__device__ __forceinline__ T fused_ld(const T* p) {
-    typedef __attribute__((address_space(1))) const T gT;
-    return __hip_atomic_load((gT*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <class T>
-__device__ __forceinline__ void fused_st(T* p, T v) {
-    typedef __attribute__((address_space(1))) T gT;
-    __hip_atomic_store((gT*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // the chain over chunk group g of episode e (CL ticks per chunk, nch chunks);
 // win / kin / start: LDS (a 512-tick window, the group's 64 merge infos and start states)
@@ -69,20 +59,14 @@ __device__ __forceinline__ FusedChain fused_group(const FrontierArgs& args, int 
     {
         const int c = c0 + lane;
         const uint64_t m = c < c1 ? fused_ld(args.cmaps + cb + c) : kIdentityMap;
-        const uint64_t inc = wave_map_scan(m);
-        uint64_t excl = shfl_up_u64(inc, 1);
-        if (lane == 0) excl = kIdentityMap;
-        const uint32_t st = map_get(excl, cs.st);
+        const uint32_t st = chunk_starts(m, cs.st, lane);
         int tr = 0;
         if (c < c1) {
             start[lane] = (uint8_t)st;
             kin[lane] = fused_ld(args.kinfo + cb + c);
-            tr = (int)fused_ld(args.ctr32 + (cb + c) * 8 + st);
+            tr = frontier_trades<SharedLd>(args.ctr32, cb + c, st);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) tr += __shfl_xor(tr, o, kWave);
-        cs.tr += tr;
-        cs.st = map_get(readlane64(inc, kWave - 1), cs.st);
+        cs.tr += wave_sum_i32(tr);
     }
     __syncthreads();  // start / kin before the gathers read them
     const double* __restrict__ rew = args.rew;
@@ -99,18 +83,8 @@ __device__ __forceinline__ FusedChain fused_group(const FrontierArgs& args, int 
 #pragma unroll
         for (int q = 0; q < kG; ++q) {
             const int i0 = (q * kWave + lane) * 4;
-            if (i0 < n) {
-                const int cl = (w0 - t0 + i0) / CL, u = w0 - t0 + i0 - cl * CL;  // chunk within the group
-                const uint32_t ki = kin[cl];
-                const int kc = (int)(ki & kKinfoTick);
-                const int64_t pst = start[cl], pp0 = ki >> 29;
-                const int64_t rb = base + frontier_row(u, cl);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int jj = min(j, n - 1 - i0);
-                    r[q][j] = fused_ld(rew + (u + jj >= kc ? pp0 : pst) * rs + rb + (int64_t)jj * kFrontierLanes);
-                }
-            }
+            if (i0 < n)  // (ticks counted within the group)
+                frontier_gather4<SharedLd, false>(r[q], rew, start, kin, base, CL, rs, w0 - t0 + i0, n - i0);
         }
     };
     double S = cs.S;
@@ -126,26 +100,10 @@ __device__ __forceinline__ FusedChain fused_group(const FrontierArgs& args, int 
         }
         __syncthreads();
         if (w0 + kFusedWin < t1) gather(w0 + kFusedWin);
-        // lane 0 adds the window in order from LDS, 32 values per round trip
-        // (exact_sum_window's sequential chain; on one lane rather than all 64 the
-        // walks sharing the SIMD lose less of the vector pipe: config 5's launch
-        // 1 270-1 285 -> 1 250-1 256 us, profiles/r06_fused/NOTES.md)
-        if (lane == 0) {
-        const double2* p = reinterpret_cast<const double2*>(win);
-        int i = 0;
-        const int nc = n & ~31;
-        for (; i < nc; i += 32) {
-            double2 v[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) v[j] = p[i / 2 + j];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                S += v[j].x;
-                S += v[j].y;
-            }
-        }
-        for (; i < n; ++i) S += win[i];
-        }
+        // lane 0 adds the window in order from LDS (seq_chain; on one lane rather
+        // than all 64 the walks sharing the SIMD lose less of the vector pipe:
+        // config 5's launch 1 270-1 285 -> 1 250-1 256 us, profiles/r06_fused/NOTES.md)
+        if (lane == 0) S = seq_chain(S, win, n);
         S = __longlong_as_double((long long)readlane64((uint64_t)__double_as_longlong(S), 0));
         __syncthreads();  // the window is read before the next one is written
     }
@@ -184,36 +142,12 @@ __device__ __forceinline__ void fused_ship(const FrontierArgs& args, int e, int 
     }
 }
 
-// the episode's record and the generation tail (sgmm_rollout.hip generation_tail /
-// tail_run, mode 3)
+// the episode's record and the generation tail (the tell's argmax, StepArgs mode 3)
 __device__ __forceinline__ void fused_finish(const FrontierArgs& args, int e, FusedChain cs) {
     const EpArrays& ep = args.ep;
     const int lane = (int)threadIdx.x;
-    double total = cs.S;
-    if (lane == 0) {
-        if (cs.tr == 0) total -= args.params[ep.param[e]].idle_penalty;  // drl_engine.py:64-65
-        store_record(args.fitness, args.trades, e, total, cs.tr);
-    }
-    const StepArgs& sa = args.step;
-    if (!sa.st) return;
-    const int n_eps = sa.pop_eps > 0 ? sa.pop_eps : args.n_eps;
-    const int k = sa.pop_eps > 0 ? e / sa.pop_eps : 0;
-    int last = 0;
-    if (lane == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        last = __hip_atomic_fetch_add(&sa.st[k].arrivals, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == n_eps - 1;
-    }
-    if (!__shfl(last, 0, kWave)) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // compiler order only: loads after the ticket
-    sgmm_ga_state* st = sa.st + k;
-    float* mm = sa.master_mm + (int64_t)k * sa.n_mm;
-    float* ma = sa.master_adv ? sa.master_adv + (int64_t)k * sa.n_adv : nullptr;
-    sgmm_ga_history* hist = sa.history ? sa.history + (int64_t)k * sa.hist_cap : nullptr;
-    const uint64_t seed = sa.seeds ? sa.seeds[k] : sa.seed;
-    const double* fit = args.fitness + (int64_t)k * n_eps;
-    const int32_t* trd = args.trades + (int64_t)k * n_eps;
-    tell_wave<true, false>(st, fit, trd, sa.P, mm, ma, sa.n_mm, sa.n_adv, seed, hist, sa.hist_cap);
-    if (lane == 0) st->arrivals = 0;
+    if (lane == 0) finish_record(args.params, ep, args.fitness, args.trades, e, cs.S, cs.tr);
+    if (args.step.st) population_arrive(args.step, args.fitness, args.trades, e, 1, args.n_eps, lane);
 }
 
 // after the walk of group cg (ng groups with chunks, at most 2): sum what this wave

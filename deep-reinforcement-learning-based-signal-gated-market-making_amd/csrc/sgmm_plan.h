@@ -36,10 +36,7 @@ constexpr int kScanThreads = 1024;  // path-scan workgroup
 constexpr int kScanAt1024 = 256;  // path-scan workgroup: 1024 threads up to this many episodes,
 constexpr int kScanAt512 = 512;   // 256 up to this many, one wave above
 constexpr int kScanArlAt1024 = 1024;  // adversary path scan: 1024 threads up to this many, kScanBlock above
-#ifndef SGMM_LANES_W
-#define SGMM_LANES_W 4
-#endif
-constexpr int kLanesW = SGMM_LANES_W;       // episodes per lanes-scan workgroup (the plan picks 2 or 4 per launch)
+constexpr int kLanesW = 4;          // episodes per lanes-scan workgroup (the plan picks 2 or 4 per launch)
 constexpr int kReorderMaxPops = 64;
 
 // ticks per chunk with nw waves (64 nw chunks) per episode

@@ -1,6 +1,7 @@
 // sgmm_rollout.h -- device layout and helpers shared by the rollout translation
-// units (sgmm_rollout.hip: path scans, host entry points; sgmm_table.hip: the
-// policy tables; sgmm_frontier.hip: the frontier kernel).
+// units (sgmm_rollout.hip: host entry points and the launch of a batch;
+// sgmm_table.hip: the policy tables; sgmm_frontier.hip: the frontier kernel;
+// sgmm_scan.hip: the path scans, their shared pieces in sgmm_scan.h).
 #pragma once
 
 #include "sgmm_device.h"
@@ -321,5 +322,27 @@ void launch_policy_table(PolicyKernel kind, int hidden, bool arl, int nsi, int m
                          double* rew, const ReorderJob* rj, hipStream_t s);
 // the walk-order job alone (k_walk_reorder)
 void launch_walk_reorder(const ReorderJob& job, hipStream_t s);
+
+// ------------------------------------------------------------------ path scan launches (sgmm_scan.hip)
+// What the policy kernel left in the workspace and where the records go
+struct ScanArgs {
+    EpArrays ep;  // frontier launches: with the plan's groups (ngrp, g0, gtail, whole)
+    const sgmm_env_params* params;
+    int32_t inv_min, nsi;
+    int32_t n;  // episodes
+    const uint64_t* cmaps;
+    const uint64_t* ctr;  // the table's byte-packed u64 counts or the frontier's u32[8] records
+    const uint32_t* kinfo;
+    const uint64_t* fills;  // adversary: the fill codes
+    const double* rew;
+    double* fitness;
+    int32_t* trades;
+    StepArgs step;
+};
+// executes plan.scan (Wave, Lanes or Arl; Fused runs inside the frontier launch)
+// with the plan's grid, workgroup and sum method
+void launch_path_scan(const LaunchPlan& plan, const ScanArgs& a, hipStream_t s);
+// init + values[0] + values[1] + ... in sequential float64 order (k_ordered_sum)
+void launch_ordered_sum(const double* values, int64_t n, double init, double* out, hipStream_t s);
 
 }  // namespace sgmm

@@ -349,3 +349,47 @@ def test_frontier_lanes_scan_inventory_ranges(sgmm, oracle, plan, caps):
     fit, trd, wf, wt = _run(sgmm, oracle, lens, 16, seed=73, caps=caps, sigma=0.6, nan_frac=0.03, fee=2e-5)
     assert np.array_equal(trd, wt)
     assert np.array_equal(fit, wf)
+
+
+def test_every_scan_agrees(sgmm, oracle, plan):
+    """One ragged batch through every path scan the plan can name -- they are
+    built from one set of pieces (sgmm_scan.h), so one batch goes through all of
+    their callers: the one-workgroup scan at each width (64 / 256 / 512 / 1024
+    threads) with both sum methods, the lanes scan with 2 and 4 episodes per
+    workgroup and the scan fused into the walks, each with 1 and 2 chunk groups
+    and with 5 and 8 inventory states.  Lengths around every scan's own edges:
+    empty, 1, 3-5 (one 4-tick gather), 63-65, 511-513 (the lanes and fused
+    windows), 1023-1025 (the one-wave scan's window), 4095-4097 (the 16-wave
+    window).  The lanes and fused scans sum with the sequential chain only
+    (resolve_plan gives another scan with seq_sum = 0), so they run with
+    seq_sum = 1; nothing else is left out.  A second batch of 17 episodes is no
+    multiple of either lanes width.  Fitness and trades equal the oracle's bit
+    for bit; the profile shows whether a scan launch ran."""
+    from sgmm_amd import _lib
+    edges = [0, 1, 3, 4, 5, 63, 64, 65, 511, 512, 513, 1023, 1024, 1025, 4095, 4096, 4097]
+    lens = edges + [2, 255, 2049]
+    assert len(lens) % 4 == 0 and len(edges) % 2 == 1
+    wave = [dict(scan_threads=nt, seq_sum=sq, lanes_scan=0, fused_scan=0)
+            for nt in (64, 256, 512, 1024) for sq in (0, 1)]
+    lanes = [dict(scan_threads=-1, seq_sum=1, lanes_scan=w, fused_scan=0) for w in (2, 4)]
+    fused = [dict(scan_threads=-1, seq_sum=1, lanes_scan=0, fused_scan=1)]
+    ran = 0
+    for caps in ((2, -2), (3, -4)):
+        for groups in (1, 2):
+            for batch, scans in ((lens, wave + lanes + fused), (edges, lanes)):
+                for knobs in scans:
+                    plan(policy_path="frontier", groups=groups, **knobs)
+                    _lib.profile_read()
+                    _lib.profile_enable(True)
+                    try:
+                        fit, trd, wf, wt = _run(sgmm, oracle, batch, 16, seed=83, caps=caps, sigma=0.5)
+                        kinds = _lib.profile_read()
+                    finally:
+                        _lib.profile_enable(False)
+                    what = (caps, groups, len(batch), knobs)
+                    assert ("path_scan" in kinds) == (knobs["fused_scan"] == 0), what
+                    assert np.array_equal(trd, wt), what
+                    assert np.array_equal(fit, wf), what
+                    ran += 1
+    assert ran == 2 * 2 * (8 + 2 + 1 + 2)
+    assert wt.max() > 0 and fit[0] == -50.0

@@ -1,6 +1,6 @@
 """Diagnostic: path-scan phase cycles on a config-3-shaped batch (stamped
 library, frontier chunks): K populations x P individuals x (4560-tick training
-+ 912-tick validation episode), H=32.  Slots (sgmm_rollout.hip SGMM_STAMP):
++ 912-tick validation episode), H=32.  Slots (sgmm_scan.hip SGMM_STAMP):
 0 entry, 1 chunk starts + trades, 2 rewards of the last window in LDS, 8
 approximate starts, 9 run records, 10 walk done, 3 end; 13 / 14 walk
 iterations / fallback blocks of the last window."""
