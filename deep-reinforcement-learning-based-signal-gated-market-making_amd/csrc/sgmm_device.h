@@ -234,6 +234,24 @@ __device__ __forceinline__ int64_t row_scan_max(int64_t v) {
     v = max(v, (int64_t)dpp64<0x118>((uint64_t)INT64_MIN, (uint64_t)v));
     return v;
 }
+// The wave reduction ladder (row shifts 1, 2, 4, 8, row broadcasts 15 and 31) on
+// 32- or 64-bit integer data: lane 63 ends with op over the whole wave.
+// op(from the lower lanes, own); a lane without a source combines `id`.
+template <int CTRL, int ROW_MASK, class T>
+__device__ __forceinline__ T dpp_int(T old, T v) {
+    if constexpr (sizeof(T) == 8) return (T)dpp64<CTRL, ROW_MASK>((uint64_t)old, (uint64_t)v);
+    else return (T)dpp32<CTRL, ROW_MASK>((uint32_t)old, (uint32_t)v);
+}
+template <class T, class Op>
+__device__ __forceinline__ T wave_ladder(T v, T id, Op op) {
+    v = op(dpp_int<0x111, 0xF>(id, v), v);
+    v = op(dpp_int<0x112, 0xF>(id, v), v);
+    v = op(dpp_int<0x114, 0xF>(id, v), v);
+    v = op(dpp_int<0x118, 0xF>(id, v), v);
+    v = op(dpp_int<0x142, 0xA>(id, v), v);
+    v = op(dpp_int<0x143, 0xC>(id, v), v);
+    return v;
+}
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, int lane) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
@@ -279,9 +297,13 @@ __device__ __forceinline__ void normal4(uint64_t seed, uint32_t stream_id, uint3
     z[3] = m1 * s1;
 }
 
-// ask() of one individual, 4 consecutive parameters (models/model.py:65-71).
-// out = master + (z * (float)sigma): the reference's randn_like * sigma in
-// float32, then the float32 add (model.py:69-70).
+// ask() (models/model.py:65-71) of one parameter: master + (z * (float)sigma),
+// the reference's randn_like * sigma in float32, then the float32 add
+// (model.py:69-70); and of 4 consecutive parameters of one individual.
+__device__ __forceinline__ float ask1(float m, float z, float sig) {
+    const float noise = z * sig;
+    return m + noise;
+}
 __device__ __forceinline__ void ask_row4(const float* __restrict__ master, int64_t n_params,
                                          float sig, uint64_t seed, uint32_t sid, uint32_t gen,
                                          uint32_t indiv, int64_t k4, float* dst) {
@@ -290,10 +312,7 @@ __device__ __forceinline__ void ask_row4(const float* __restrict__ master, int64
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int64_t k = 4 * k4 + q;
-        if (k < n_params) {
-            const float noise = z[q] * sig;
-            dst[q] = master[k] + noise;
-        }
+        if (k < n_params) dst[q] = ask1(master[k], z[q], sig);
     }
 }
 
@@ -308,18 +327,12 @@ __device__ __forceinline__ bool better(double a, int ia, double b, int ib) {
 
 // Population results gathered shard by shard: individual i's value lives in
 // shard i / n at byte offset (i / n) * stride, element i % n (n <= 0: one
-// contiguous array).  This is the layout of an all-gather of per-rank records.
+// contiguous array).  This is the layout of an all-gather of per-rank records
+// (read with shard_ld, sgmm_ga_device.h).
 struct ShardView {
     int32_t n;
     int64_t stride;
 };
-
-template <class T>
-__device__ __forceinline__ T shard_at(const T* __restrict__ base, ShardView v, int i) {
-    if (v.n <= 0) return base[i];
-    const char* p = reinterpret_cast<const char*>(base) + (int64_t)(i / v.n) * v.stride;
-    return reinterpret_cast<const T*>(p)[i % v.n];
-}
 
 constexpr int kMaxStepParams = 4096;  // largest genome a one-workgroup GA step stages in LDS
 

@@ -39,8 +39,8 @@ __device__ unsigned int g_thwid[kStampWaves][2];  // HW_ID, XCC_ID of each wave
 // group 0 to continue with.  The
 // chain's last wave adds the idle penalty (drl_engine.py:64-65), stores the record,
 // and the last record of a population runs the generation tail (tell_wave, the
-// argmax of StepArgs mode 3; mode 1's master regeneration would take the walk
-// loop's registers).
+// argmax of StepArgs mode kStepArgmax; the masters are regenerated in the
+// validation launch's tail).
 struct FusedChain {
     double S;     // the running sum
     uint32_t st;  // the state the path enters the next chunk in (0 .. nsi - 1)

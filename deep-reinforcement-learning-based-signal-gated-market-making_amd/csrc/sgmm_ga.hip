@@ -37,75 +37,22 @@ __global__ __launch_bounds__(kTellBlock) void k_ga_tell(
     const float* __restrict__ pop_mm, int64_t pop_mm_stride, float* __restrict__ master_adv,
     const float* __restrict__ pop_adv, int64_t pop_adv_stride, int64_t n_mm, int64_t n_adv,
     uint64_t seed, sgmm_ga_history* __restrict__ history, int32_t hist_cap) {
-    __shared__ double sv[2][kTellBlock];
-    const uint32_t gen = (uint32_t)st->gen;
-    sgmm_ga_history* hist = (history && st->gen < hist_cap) ? history + st->gen : nullptr;
-    __shared__ int si[2][kTellBlock];
-    const int tid = threadIdx.x;
-    double bv = 0.0, av = 0.0;
-    int bi = -1, aj = -1;
-    for (int i = tid; i < P; i += kTellBlock) {
-        const double f = fit[i];
-        if (bi < 0 || better(f, i, bv, bi)) { bv = f; bi = i; }
-        if (aj < 0 || better(-f, i, av, aj)) { av = -f; aj = i; }
-    }
-    sv[0][tid] = bv; si[0][tid] = bi;
-    sv[1][tid] = av; si[1][tid] = aj;
-    __syncthreads();
-    for (int w = kTellBlock / 2; w > 0; w >>= 1) {
-        if (tid < w) {
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const int io = si[r][tid + w];
-                if (io >= 0 && (si[r][tid] < 0 || better(sv[r][tid + w], io, sv[r][tid], si[r][tid]))) {
-                    sv[r][tid] = sv[r][tid + w];
-                    si[r][tid] = io;
-                }
-            }
-        }
-        __syncthreads();
-    }
-    const int best = si[0][0], abest = si[1][0];
-    const double sig_mm = st->sigma_mm, sig_adv = st->sigma_adv;
-    __syncthreads();
+    __shared__ double sv[2 * kTellBlock];
+    __shared__ int si[2 * kTellBlock];
+    const int32_t gen = st->gen;
+    const float sig_mm = (float)st->sigma_mm, sig_adv = (float)st->sigma_adv;
+    int best, abest;
+    block_argmax2<false>(fit, ShardView{0, 0}, P, best, abest, sv, si);
     // new masters (model.py:75): copy the host-supplied row, or regenerate
     // the ask() of that individual in place (counter-based RNG)
-    const int64_t nk_mm = (n_mm + 3) / 4;
-    for (int64_t k4 = tid; k4 < nk_mm; k4 += kTellBlock) {
-        if (pop_mm) {
-            for (int q = 0; q < 4; ++q)
-                if (4 * k4 + q < n_mm) master_mm[4 * k4 + q] = pop_mm[best * pop_mm_stride + 4 * k4 + q];
-        } else {
-            float v[4];
-            ask_row4(master_mm, n_mm, (float)sig_mm, seed, 0u, gen, (uint32_t)best, k4, v);
-            for (int q = 0; q < 4; ++q)
-                if (4 * k4 + q < n_mm) master_mm[4 * k4 + q] = v[q];
-        }
-    }
+    if (pop_mm) copy_row(master_mm, pop_mm + best * pop_mm_stride, n_mm);
+    else regen_master_block(master_mm, nullptr, n_mm, sig_mm, seed, 0u, (uint32_t)gen, best);
     if (master_adv) {
-        const int64_t nk_adv = (n_adv + 3) / 4;
-        for (int64_t k4 = tid; k4 < nk_adv; k4 += kTellBlock) {
-            if (pop_adv) {
-                for (int q = 0; q < 4; ++q)
-                    if (4 * k4 + q < n_adv) master_adv[4 * k4 + q] = pop_adv[abest * pop_adv_stride + 4 * k4 + q];
-            } else {
-                float v[4];
-                ask_row4(master_adv, n_adv, (float)sig_adv, seed, 1u, gen, (uint32_t)abest, k4, v);
-                for (int q = 0; q < 4; ++q)
-                    if (4 * k4 + q < n_adv) master_adv[4 * k4 + q] = v[q];
-            }
-        }
+        if (pop_adv) copy_row(master_adv, pop_adv + abest * pop_adv_stride, n_adv);
+        else regen_master_block(master_adv, nullptr, n_adv, sig_adv, seed, 1u, (uint32_t)gen, abest);
     }
-    if (tid == 0) {
-        st->best_idx = best;
-        st->adv_best_idx = abest;
-        st->last_train_f = fit[best];
-        if (hist) {
-            hist->train_f = fit[best];
-            hist->train_trades = trades ? trades[best] : 0;
-            hist->best_idx = best;
-        }
-    }
+    if (threadIdx.x == 0)
+        tell_commit(st, hist_row(history, gen, hist_cap), best, abest, fit[best], trades ? trades[best] : 0);
 }
 
 __global__ __launch_bounds__(kTellBlock) void k_ga_val_update(
@@ -192,46 +139,44 @@ __global__ __launch_bounds__(kStepBlock) void k_ga_step_multi(
 
 using namespace sgmm;
 
-extern "C" int sgmm_ga_step_multi(const sgmm_populations* pops, const double* fitness,
-                                  const int32_t* trades, const double* val_fitness,
-                                  const int32_t* val_trades, int64_t fit_pop_stride,
-                                  int64_t trades_pop_stride, int32_t shard_n, int64_t shard_stride,
-                                  void* stream) {
+// sgmm_ga_step_multi (label "ga_step") and, with no validation records,
+// sgmm_ga_tell_multi ("ga_tell"): the checks, the PopsArg and the launch
+static int step_multi(const char* label, bool tell_only, const sgmm_populations* pops, const double* fitness,
+                      const int32_t* trades, const double* val_fitness, const int32_t* val_trades,
+                      int64_t fit_pop_stride, int64_t trades_pop_stride, int32_t shard_n, int64_t shard_stride,
+                      void* stream) {
     clear_error();
     SGMM_REQUIRE(pops && pops->n_pop > 0 && pops->P > 0, "bad populations");
     SGMM_REQUIRE(supported_hidden(pops->hidden), "hidden=%d unsupported", pops->hidden);
-    SGMM_REQUIRE(pops->states && pops->masters_mm && pops->seeds && fitness && val_fitness, "null pointer");
+    SGMM_REQUIRE(pops->states && pops->masters_mm && pops->seeds && fitness && (tell_only || val_fitness),
+                 "null pointer");
     SGMM_REQUIRE(shard_n <= 0 || shard_stride >= 8LL * shard_n, "shard_stride < 8 * shard_n");
     const int64_t n_mm = (int64_t)pops->hidden * pops->hidden + 7 * pops->hidden + 2;
     SGMM_REQUIRE(n_mm <= kMaxStepParams, "genome too large for the GA step");  // the LDS master stage
     PopsArg pa{pops->states, pops->masters_mm, pops->masters_adv, pops->best_masters, pops->seeds,
                pops->history, pops->history_cap, pops->P, n_mm, pops->masters_adv ? 1250 : 0};
-    ProfScope prof("ga_step", as_stream(stream));
+    ProfScope prof(label, as_stream(stream));
     hipLaunchKernelGGL(k_ga_step_multi, dim3(pops->n_pop), dim3(kStepBlock), 0, as_stream(stream), pa,
                        fitness, trades, val_fitness, val_trades, fit_pop_stride, trades_pop_stride,
-                       ShardView{shard_n, shard_stride}, 0);
+                       ShardView{shard_n, shard_stride}, tell_only ? 1 : 0);
     SGMM_LAUNCHED();
     return SGMM_OK;
+}
+
+extern "C" int sgmm_ga_step_multi(const sgmm_populations* pops, const double* fitness,
+                                  const int32_t* trades, const double* val_fitness,
+                                  const int32_t* val_trades, int64_t fit_pop_stride,
+                                  int64_t trades_pop_stride, int32_t shard_n, int64_t shard_stride,
+                                  void* stream) {
+    return step_multi("ga_step", false, pops, fitness, trades, val_fitness, val_trades, fit_pop_stride,
+                      trades_pop_stride, shard_n, shard_stride, stream);
 }
 
 extern "C" int sgmm_ga_tell_multi(const sgmm_populations* pops, const double* fitness, const int32_t* trades,
                                   int64_t fit_pop_stride, int64_t trades_pop_stride, int32_t shard_n,
                                   int64_t shard_stride, void* stream) {
-    clear_error();
-    SGMM_REQUIRE(pops && pops->n_pop > 0 && pops->P > 0, "bad populations");
-    SGMM_REQUIRE(supported_hidden(pops->hidden), "hidden=%d unsupported", pops->hidden);
-    SGMM_REQUIRE(pops->states && pops->masters_mm && pops->seeds && fitness, "null pointer");
-    SGMM_REQUIRE(shard_n <= 0 || shard_stride >= 8LL * shard_n, "shard_stride < 8 * shard_n");
-    const int64_t n_mm = (int64_t)pops->hidden * pops->hidden + 7 * pops->hidden + 2;
-    SGMM_REQUIRE(n_mm <= kMaxStepParams, "genome too large for the GA step");
-    PopsArg pa{pops->states, pops->masters_mm, pops->masters_adv, pops->best_masters, pops->seeds,
-               pops->history, pops->history_cap, pops->P, n_mm, pops->masters_adv ? 1250 : 0};
-    ProfScope prof("ga_tell", as_stream(stream));
-    hipLaunchKernelGGL(k_ga_step_multi, dim3(pops->n_pop), dim3(kStepBlock), 0, as_stream(stream), pa,
-                       fitness, trades, nullptr, nullptr, fit_pop_stride, trades_pop_stride,
-                       ShardView{shard_n, shard_stride}, 1);
-    SGMM_LAUNCHED();
-    return SGMM_OK;
+    return step_multi("ga_tell", true, pops, fitness, trades, nullptr, nullptr, fit_pop_stride, trades_pop_stride,
+                      shard_n, shard_stride, stream);
 }
 
 extern "C" int sgmm_ga_step(sgmm_ga_state* state, const double* fitness, const int32_t* trades,

@@ -1,6 +1,14 @@
 // sgmm_ga_device.h -- the generation boundary as device code, shared by the
-// standalone GA kernels (sgmm_ga.hip) and the fused rollout launches
-// (sgmm_rollout.hip, whose last workgroup runs it).
+// standalone GA kernels (sgmm_ga.hip) and the tails inside the rollout launches
+// (sgmm_scan.hip: tail_run and validation_tail; sgmm_scan.h: population_arrive
+// of the lanes scan and of the frontier's fused scan).
+//
+// Each piece of the boundary's semantics is here once, cut the way the model
+// tests/ga_model.py is: tell_commit (ga_model.tell's record), val_commit
+// (ga_model.val_update) on a GaSnap of the state, hist_row, regen4 (master <-
+// ask(best)), and better / argmax_merge / argmax_key under every argmax.  The
+// three argmax schedules -- block_argmax2, ga_step_fused's with its payload,
+// tell_wave's blocked loads -- are measured designs and stay apart.
 //
 // Reference: NeuroEvolution.tell (models/model.py:73-76) and the validation /
 // sigma-decay block of DRLEngine.train (Env/drl_engine.py:119-171).
@@ -10,9 +18,9 @@
 
 namespace sgmm {
 
-// ---------------------------------------------------------------- fused boundary
 constexpr int kStepBlock = 1024;
 
+// ---------------------------------------------------------------- records and argmax
 // Loads of the fitness records.  HANDOFF: they were stored in this launch by
 // other workgroups with write-through (sc1) stores, so every load of them is a
 // global sc1 load (MI355X_MICROARCH.md, inter-workgroup visibility, row 1:
@@ -28,6 +36,7 @@ __device__ __forceinline__ T ld_rec(const T* p) {
     }
 }
 
+// individual i's record in a ShardView
 template <bool HANDOFF, class T>
 __device__ __forceinline__ T shard_ld(const T* __restrict__ base, ShardView v, int i) {
     if (v.n <= 0) return ld_rec<HANDOFF>(base + i);
@@ -41,30 +50,24 @@ __device__ __forceinline__ void argmax_merge(double& bv, int& bi, double ov, int
     bi = take ? oi : bi;
 }
 
-// np.argmax over one wave (first index on ties, NaN first), lanes with
-// valid: a NaN ballot, a max butterfly, a ballot of the lanes equal to the
-// max.  Returns the winning lane (-1: no valid lane) and its value.
+// order-preserving unsigned key: -0 == +0, NaN above everything
 __device__ __forceinline__ uint64_t argmax_key(double f) {
-    // order-preserving unsigned key: -0 == +0, NaN above everything
     if (f != f) return ~0ull;
     const uint64_t b = (uint64_t)__double_as_longlong(f == 0.0 ? 0.0 : f);
     return (b >> 63) ? ~b : (b | (1ull << 63));
 }
 
-// wave maximum of an unsigned 64-bit value (DPP row shifts and row
-// broadcasts, integer data only), read from lane 63
+// wave maximum / minimum (wave_ladder: integer data only), uniform
 __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#define SGMM_XSTEP(CTRL, RM)                              \
-    {                                                     \
-        const uint64_t t_ = dpp64<CTRL, RM>(0ull, v);     \
-        v = t_ > v ? t_ : v;                              \
-    }
-    SGMM_XSTEP(0x111, 0xF) SGMM_XSTEP(0x112, 0xF) SGMM_XSTEP(0x114, 0xF)
-    SGMM_XSTEP(0x118, 0xF) SGMM_XSTEP(0x142, 0xA) SGMM_XSTEP(0x143, 0xC)
-#undef SGMM_XSTEP
-    return readlane64(v, kWave - 1);
+    return readlane64(wave_ladder(v, (uint64_t)0, [](uint64_t t, uint64_t x) { return t > x ? t : x; }), kWave - 1);
+}
+__device__ __forceinline__ int wave_min_i32(int v) {
+    return __builtin_amdgcn_readlane(wave_ladder(v, INT32_MAX, [](int t, int x) { return t < x ? t : x; }), kWave - 1);
 }
 
+// np.argmax over one wave (first index on ties, NaN first), lanes with
+// valid: a key maximum, a ballot of the lanes equal to it.  Returns the
+// winning lane (-1: no valid lane) and its value.
 __device__ __forceinline__ int wave_argmax_first(double f, bool valid, double& bv) {
     const uint64_t k = valid ? argmax_key(f) : 0ull;
     const uint64_t m = wave_max_u64(k);
@@ -72,6 +75,14 @@ __device__ __forceinline__ int wave_argmax_first(double f, bool valid, double& b
     const int l = hit ? __ffsll((unsigned long long)hit) - 1 : -1;
     bv = __longlong_as_double((long long)readlane64((uint64_t)__double_as_longlong(f), l < 0 ? 0 : l));
     return l;
+}
+
+// first index of the largest key over the wave (lane candidates (key, idx),
+// idx < 0: none); -1 when no lane has a candidate
+__device__ __forceinline__ int wave_best_index(uint64_t key, int idx) {
+    const uint64_t m = wave_max_u64(idx >= 0 ? key : 0ull);  // valid keys are > 0
+    const int c = wave_min_i32(idx >= 0 && key == m ? idx : INT32_MAX);
+    return c == INT32_MAX ? -1 : c;
 }
 
 // np.argmax of fit and of -fit (first index on ties, NaN first) over the
@@ -125,18 +136,43 @@ __device__ void block_argmax2(const double* __restrict__ fit, ShardView sv_, int
     abest = si[nt];
 }
 
-// master <- ask(best) in place; staged copy to LDS for the next ask
-__device__ void regen_master(float* __restrict__ master, float* lds_master, int64_t n, float sig,
-                             uint64_t seed, uint32_t sid, uint32_t gen, int best) {
-    for (int64_t k4 = threadIdx.x; k4 < (n + 3) / 4; k4 += blockDim.x) {
-        float v[4];
-        ask_row4(master, n, sig, seed, sid, gen, (uint32_t)best, k4, v);
-        for (int q = 0; q < 4; ++q)
-            if (4 * k4 + q < n) {
-                master[4 * k4 + q] = v[q];
-                lds_master[4 * k4 + q] = v[q];
-            }
+// ---------------------------------------------------------------- master <- ask(best)
+__device__ __forceinline__ void load4(const float* __restrict__ master, int64_t n, int64_t k4, float (&m)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) m[q] = 4 * k4 + q < n ? master[4 * k4 + q] : 0.0f;
+}
+
+// parameters 4 k4 .. 4 k4 + 3 of master <- ask(best), from their current values
+// m (read before they are overwritten); the new values into copy too when given
+__device__ __forceinline__ void regen4(float* __restrict__ master, float* copy, int64_t n, int64_t k4,
+                                       const float (&m)[4], float sig, uint64_t seed, uint32_t sid,
+                                       uint32_t gen, int best) {
+    float z[4];
+    normal4(seed, sid, gen, (uint32_t)best, (uint32_t)k4, z);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (4 * k4 + q < n) {
+            const float v = ask1(m[q], z[q], sig);
+            master[4 * k4 + q] = v;
+            if (copy) copy[4 * k4 + q] = v;
+        }
+}
+
+// by every thread of the workgroup, 4 parameters a thread at a time.  copy:
+// ga_step_dev's LDS stage for the next ask; none for the deferred half of the
+// tell (validation_tail) and for k_ga_tell
+__device__ __forceinline__ void regen_master_block(float* __restrict__ master, float* copy, int64_t n, float sig,
+                                                   uint64_t seed, uint32_t sid, uint32_t gen, int best) {
+    for (int64_t k4 = threadIdx.x; 4 * k4 < n; k4 += blockDim.x) {
+        float m[4];
+        load4(master, n, k4, m);
+        regen4(master, copy, n, k4, m, sig, seed, sid, gen, best);
     }
+}
+
+// dst[0..n) <- src[0..n) by the workgroup
+__device__ __forceinline__ void copy_row(float* __restrict__ dst, const float* src, int64_t n) {
+    for (int64_t k = threadIdx.x; k < n; k += blockDim.x) dst[k] = src[k];
 }
 
 __device__ void ask_rows(const float* lds_master, int64_t n, float sig, uint64_t seed,
@@ -153,15 +189,27 @@ __device__ void ask_rows(const float* lds_master, int64_t n, float sig, uint64_t
     }
 }
 
-// The tell's bookkeeping when the validation runs after it (reference order,
-// drl_engine.py:119-128): best / adversary indices, the best training record,
-// the history row's training fields.  One thread.
-template <bool HANDOFF>
-__device__ __forceinline__ void tell_record(sgmm_ga_state* __restrict__ st, const double* __restrict__ fit,
-                                            const int32_t* __restrict__ trades, ShardView shard, int best,
-                                            int abest, sgmm_ga_history* __restrict__ hist) {
-    const double tf = shard_ld<HANDOFF>(fit, shard, best);
-    const int32_t ttr = trades ? shard_ld<HANDOFF>(trades, shard, best) : 0;
+// ---------------------------------------------------------------- the boundary's bookkeeping
+// row `gen` of a population's history, or null
+__device__ __forceinline__ sgmm_ga_history* hist_row(sgmm_ga_history* history, int32_t gen, int32_t cap) {
+    return history && gen < cap ? history + gen : nullptr;
+}
+
+// The state words a boundary reads, as values: a caller loads them where its
+// schedule wants them (ga_step_fused: with its other up-front loads).
+struct GaSnap {
+    int32_t gen, no_improve, patience;
+    double sigma_mm, sigma_adv, best_val, decay;
+};
+__device__ __forceinline__ GaSnap ga_snap(const sgmm_ga_state* st) {
+    return GaSnap{st->gen, st->no_improve, st->patience, st->sigma_mm, st->sigma_adv, st->best_val, st->decay};
+}
+
+// The tell's record (ga_model.tell; drl_engine.py:119-128): best / adversary
+// indices, the best's training record, the history row's training fields.
+// One thread.
+__device__ __forceinline__ void tell_commit(sgmm_ga_state* __restrict__ st, sgmm_ga_history* __restrict__ hist,
+                                            int best, int abest, double tf, int32_t ttr) {
     st->best_idx = best;
     st->adv_best_idx = abest;
     st->last_train_f = tf;
@@ -172,58 +220,65 @@ __device__ __forceinline__ void tell_record(sgmm_ga_state* __restrict__ st, cons
     }
 }
 
-// Validation bookkeeping of one population (drl_engine.py:129-160): v / vtr
-// are the validation record of the post-tell master.  Checkpoint copy
-// master -> best_master on improvement (strictly greater; NaN never improves),
-// sigma decay after `patience` generations without improvement, the history
-// row's validation fields, gen + 1.  Every thread of the workgroup calls
-// (v identical in all); `flag` is one int of LDS scratch.
+// strictly greater: a tie and NaN never improve (drl_engine.py:130-131)
+__device__ __forceinline__ int val_improves(double v, double best_val) { return v > best_val; }
+
+// The validation bookkeeping (ga_model.val_update; drl_engine.py:129-160) on the
+// validation record v / vtr of the post-tell master: best_val on improvement,
+// sigma decay after `patience` generations without one, the history row's
+// validation fields, gen + 1.  One thread; the caller copies the checkpoint.
+struct ValOut {
+    int improved;
+    double sigma_mm, sigma_adv;  // after the decay
+};
+__device__ __forceinline__ ValOut val_commit(sgmm_ga_state* __restrict__ st, sgmm_ga_history* __restrict__ hist,
+                                             const GaSnap& s, double v, int32_t vtr) {
+    const int improved = val_improves(v, s.best_val);
+    int32_t no_improve = improved ? 0 : s.no_improve + 1;
+    double smm = s.sigma_mm, sadv = s.sigma_adv;
+    int decayed = 0;
+    if (no_improve >= s.patience) {  // drl_engine.py:155-160
+        smm *= s.decay;
+        sadv *= s.decay;
+        no_improve = 0;
+        decayed = 1;
+    }
+    if (improved) st->best_val = v;
+    st->sigma_mm = smm;
+    st->sigma_adv = sadv;
+    st->no_improve = no_improve;
+    st->improved = improved;
+    st->decayed = decayed;
+    st->last_val_f = v;
+    st->gen = s.gen + 1;
+    if (hist) {
+        hist->val_f = v;
+        hist->val_trades = vtr;
+        hist->sigma_after = smm;
+        hist->flags = improved | (decayed << 1);
+    }
+    return ValOut{improved, smm, sadv};
+}
+
+// val_commit and the checkpoint copy master -> best_master on improvement, by
+// one workgroup: every thread calls (v identical in all); `flag` is one int of
+// LDS scratch.
 __device__ __forceinline__ void val_update_dev(sgmm_ga_state* __restrict__ st, double v, int32_t vtr,
                                                const float* __restrict__ master, float* __restrict__ best_master,
                                                int64_t n, sgmm_ga_history* __restrict__ history,
                                                int32_t hist_cap, int* flag) {
     if (threadIdx.x == 0) {
-        const int32_t gen = st->gen;
-        sgmm_ga_history* hist = (history && gen < hist_cap) ? history + gen : nullptr;
-        const int improved = v > st->best_val;
-        int decayed = 0;
-        int32_t no_improve = st->no_improve;
-        if (improved) {
-            st->best_val = v;
-            no_improve = 0;
-        } else {
-            no_improve += 1;
-        }
-        double smm = st->sigma_mm, sadv = st->sigma_adv;
-        if (no_improve >= st->patience) {  // drl_engine.py:155-160
-            smm *= st->decay;
-            sadv *= st->decay;
-            no_improve = 0;
-            decayed = 1;
-        }
-        st->sigma_mm = smm;
-        st->sigma_adv = sadv;
-        st->no_improve = no_improve;
-        st->improved = improved;
-        st->decayed = decayed;
-        st->last_val_f = v;
-        st->gen = gen + 1;
-        if (hist) {
-            hist->val_f = v;
-            hist->val_trades = vtr;
-            hist->sigma_after = smm;
-            hist->flags = improved | (decayed << 1);
-        }
-        *flag = improved;
+        const GaSnap s = ga_snap(st);
+        *flag = val_commit(st, hist_row(history, s.gen, hist_cap), s, v, vtr).improved;
     }
     __syncthreads();
-    if (*flag && best_master)
-        for (int64_t k = threadIdx.x; k < n; k += blockDim.x) best_master[k] = master[k];
+    if (*flag && best_master) copy_row(best_master, master, n);
 }
 
 // One generation boundary, executed by one whole workgroup (power-of-two
 // size): tell both evolvers, validation bookkeeping, sigma decay, history
-// row, and optionally the next generation's ask of [i0, i0+n).
+// row, and optionally the next generation's ask of [i0, i0+n).  tell_only: the
+// tell alone (sgmm_ga_tell_multi; the validation follows in its own launches).
 // LDS scratch: sv[2*nt] doubles, si[2*nt] ints, lm[n_mm], la[n_adv] floats.
 // HANDOFF: the fitness records come from other workgroups of this launch
 // (sc1 loads, see ld_rec).
@@ -236,82 +291,41 @@ __device__ void ga_step_dev(sgmm_ga_state* __restrict__ st, const double* __rest
                             uint64_t seed, sgmm_ga_history* __restrict__ history, int32_t hist_cap,
                             float* __restrict__ next_mm, float* __restrict__ next_adv, int32_t i0,
                             int32_t n, double* sv, int* si, float* lm, float* la, bool tell_only = false) {
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const uint32_t gen = (uint32_t)st->gen;
-    sgmm_ga_history* hist = (history && st->gen < hist_cap) ? history + st->gen : nullptr;
+    const GaSnap s = ga_snap(st);
+    const uint32_t gen = (uint32_t)s.gen;
     int best, abest;
     block_argmax2<HANDOFF>(fit, shard, P, best, abest, sv, si);
-    const float sig_mm = (float)st->sigma_mm, sig_adv = (float)st->sigma_adv;
     __syncthreads();  // sv/si are reused below
-    // tell (model.py:73-76; drl_engine.py:119-125)
-    regen_master(master, lm, n_mm, sig_mm, seed, 0u, gen, best);
-    if (master_adv) regen_master(master_adv, la, n_adv, sig_adv, seed, 1u, gen, abest);
-    if (tell_only) {  // the validation of the new master follows in its own launches
-        if (tid == 0) tell_record<HANDOFF>(st, fit, trades, shard, best, abest, hist);
-        return;
-    }
-    if (tid == 0) {
-        // validation of the best (drl_engine.py:129-171); every load issued
-        // before the first dependent use
-        const double v = shard_ld<HANDOFF>(vfit, shard, best);
+    // tell (model.py:73-76; drl_engine.py:119-125), the new masters staged for the next ask
+    regen_master_block(master, lm, n_mm, (float)s.sigma_mm, seed, 0u, gen, best);
+    if (master_adv) regen_master_block(master_adv, la, n_adv, (float)s.sigma_adv, seed, 1u, gen, abest);
+    if (threadIdx.x == 0) {  // every load issued before the first dependent use
+        const bool val = !tell_only;
         const double tf = shard_ld<HANDOFF>(fit, shard, best);
+        const double v = val ? shard_ld<HANDOFF>(vfit, shard, best) : 0.0;
         const int32_t ttr = trades ? shard_ld<HANDOFF>(trades, shard, best) : 0;
-        const int32_t vtr = vtrades ? shard_ld<HANDOFF>(vtrades, shard, best) : 0;
-        const double best_val = st->best_val, decay = st->decay;
-        double smm = st->sigma_mm, sadv = st->sigma_adv;
-        int32_t no_improve = st->no_improve;
-        const int32_t patience = st->patience;
-        const int improved = v > best_val;
-        int decayed = 0;
-        if (improved) {
-            st->best_val = v;
-            no_improve = 0;
-        } else {
-            no_improve += 1;
-        }
-        if (no_improve >= patience) {
-            smm *= decay;
-            sadv *= decay;
-            no_improve = 0;
-            decayed = 1;
-        }
-        st->sigma_mm = smm;
-        st->sigma_adv = sadv;
-        st->no_improve = no_improve;
-        st->best_idx = best;
-        st->adv_best_idx = abest;
-        st->last_train_f = tf;
-        st->improved = improved;
-        st->decayed = decayed;
-        st->last_val_f = v;
-        st->gen = (int32_t)gen + 1;
-        si[0] = improved;
-        sv[0] = smm;
-        sv[1] = sadv;
-        if (hist) {
-            hist->train_f = tf;
-            hist->train_trades = ttr;
-            hist->best_idx = best;
-            hist->val_f = v;
-            hist->val_trades = vtr;
-            hist->sigma_after = smm;
-            hist->flags = improved | (decayed << 1);
+        const int32_t vtr = val && vtrades ? shard_ld<HANDOFF>(vtrades, shard, best) : 0;
+        sgmm_ga_history* hist = hist_row(history, s.gen, hist_cap);
+        tell_commit(st, hist, best, abest, tf, ttr);
+        if (val) {  // validation of the best (drl_engine.py:129-171)
+            const ValOut o = val_commit(st, hist, s, v, vtr);
+            si[0] = o.improved;
+            sv[0] = o.sigma_mm;
+            sv[1] = o.sigma_adv;
         }
     }
+    if (tell_only) return;
     __syncthreads();
-    const int improved = si[0];
-    const float next_sig_mm = (float)sv[0], next_sig_adv = (float)sv[1];
-    if (improved && best_master)
-        for (int64_t k = tid; k < n_mm; k += nt) best_master[k] = lm[k];
+    if (si[0] && best_master) copy_row(best_master, lm, n_mm);
     // ask of the next generation (model.py:65-71) from the new master / sigma
-    if (next_mm) ask_rows(lm, n_mm, next_sig_mm, seed, 0u, gen + 1, i0, n, next_mm);
-    if (next_adv && master_adv) ask_rows(la, n_adv, next_sig_adv, seed, 1u, gen + 1, i0, n, next_adv);
+    if (next_mm) ask_rows(lm, n_mm, (float)sv[0], seed, 0u, gen + 1, i0, n, next_mm);
+    if (next_adv && master_adv) ask_rows(la, n_adv, (float)sv[1], seed, 1u, gen + 1, i0, n, next_adv);
 }
 
 // The fused generation tail's GA step (sgmm_generation: one workgroup, the
 // records contiguous, P <= blockDim.x).  The same results as ga_step_dev, laid
-// out for latency: every record (sc1) and the masters are loaded up front, the
-// argmax carries the best individual's validation record through its
+// out for latency: every record (sc1), the masters and the state are loaded up
+// front, the argmax carries the best individual's validation record through its
 // shuffles, and the masters are regenerated from registers.
 constexpr int kTailSlots = 4;  // float4 master chunks per thread (n <= 16 * blockDim.x)
 
@@ -352,11 +366,7 @@ __device__ __forceinline__ void argmax_merge_p(double& bv, int& bi, double& pv, 
 __device__ __forceinline__ void load_master4(const float* __restrict__ m, int64_t n,
                                              float (&r)[kTailSlots][4]) {
 #pragma unroll
-    for (int j = 0; j < kTailSlots; ++j) {
-        const int64_t k4 = threadIdx.x + (int64_t)j * blockDim.x;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) r[j][q] = 4 * k4 + q < n ? m[4 * k4 + q] : 0.0f;
-    }
+    for (int j = 0; j < kTailSlots; ++j) load4(m, n, threadIdx.x + (int64_t)j * blockDim.x, r[j]);
 }
 
 // master <- ask(best) from the registers m; also into best_copy when given
@@ -369,15 +379,7 @@ __device__ __forceinline__ void regen_master_regs(float* __restrict__ master, fl
     for (int j = 0; j < kTailSlots; ++j) {
         const int64_t k4 = threadIdx.x + (int64_t)j * blockDim.x;
         if (4 * k4 >= n) break;
-        float z[4];
-        normal4(seed, sid, gen, (uint32_t)best, (uint32_t)k4, z);
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (4 * k4 + q < n) {
-                const float v = m[j][q] + z[q] * sig;  // ask_row4's arithmetic
-                master[4 * k4 + q] = v;
-                if (best_copy) best_copy[4 * k4 + q] = v;
-            }
+        regen4(master, best_copy, n, k4, m[j], sig, seed, sid, gen, best);
     }
 }
 
@@ -388,7 +390,7 @@ __device__ void ga_step_fused(sgmm_ga_state* __restrict__ st, const double* __re
                               float* __restrict__ master, float* __restrict__ master_adv,
                               float* __restrict__ best_master, int64_t n_mm, int64_t n_adv,
                               uint64_t seed, sgmm_ga_history* __restrict__ history, int32_t hist_cap,
-                              double* sv, int* si, float* lm, float* la, bool tell_only = false) {
+                              double* sv, int* si) {
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & (kWave - 1), wv = tid / kWave;
     const int nw = (nt + kWave - 1) / kWave;
     SGMM_TAIL_DECL
@@ -398,19 +400,16 @@ __device__ void ga_step_fused(sgmm_ga_state* __restrict__ st, const double* __re
     const bool mine = tid < P;
     if (mine) {
         f = ld_rec<HANDOFF>(fit + tid);
-        if (!tell_only) vf = ld_rec<HANDOFF>(vfit + tid);
+        vf = ld_rec<HANDOFF>(vfit + tid);
         if (trades) tr = ld_rec<HANDOFF>(trades + tid);
-        if (vtrades && !tell_only) vtr = ld_rec<HANDOFF>(vtrades + tid);
+        if (vtrades) vtr = ld_rec<HANDOFF>(vtrades + tid);
     }
     float mm[kTailSlots][4], ma[kTailSlots][4];
     load_master4(master, n_mm, mm);
     if (master_adv) load_master4(master_adv, n_adv, ma);
-    const int32_t gen_i = st->gen;
-    const uint32_t gen = (uint32_t)gen_i;
-    const double st_smm = st->sigma_mm, st_sadv = st->sigma_adv, best_val = st->best_val,
-                 decay = st->decay;
-    const int32_t no_improve0 = st->no_improve, patience = st->patience;
-    const float sig_mm = (float)st_smm, sig_adv = (float)st_sadv;
+    const GaSnap s = ga_snap(st);
+    const uint32_t gen = (uint32_t)s.gen;
+    const float sig_mm = (float)s.sigma_mm, sig_adv = (float)s.sigma_adv;
     SGMM_TAIL_STAMP(0, f + vf + mm[0][0] + sig_mm);
     // ---- argmax of fit (payload: the validation record) and of -fit: the
     // waves holding records reduce with shuffles, every thread merges their
@@ -455,150 +454,39 @@ __device__ void ga_step_fused(sgmm_ga_state* __restrict__ st, const double* __re
         argmax_merge(av, aj, sv[2 * nw + w], si[3 * nw + w]);
     }
     const int best = bi, abest = aj;
-    // every thread knows whether the validation improved (drl_engine.py:130-131)
-    const int improved = !tell_only && pv > best_val;
+    // every thread knows whether the validation improved
+    const int improved = val_improves(pv, s.best_val);
     SGMM_TAIL_STAMP(1, best + abest);
     // ---- tell (model.py:73-76; drl_engine.py:119-125), the checkpoint copy
     // of the new master written in the same pass
     regen_master_regs(master, improved ? best_master : nullptr, n_mm, mm, sig_mm, seed, 0u, gen, best);
     if (master_adv) regen_master_regs(master_adv, nullptr, n_adv, ma, sig_adv, seed, 1u, gen, abest);
     SGMM_TAIL_STAMP(2, mm[0][0]);
-    if (tell_only) {  // the validation of the new master follows in its own launches
-        if (tid == 0) {
-            st->best_idx = best;
-            st->adv_best_idx = abest;
-            st->last_train_f = bv;
-            if (history && gen_i < hist_cap) {
-                sgmm_ga_history* hist = history + gen_i;
-                hist->train_f = bv;
-                hist->train_trades = pt;
-                hist->best_idx = best;
-            }
-        }
-        SGMM_TAIL_FLUSH;
-        return;
-    }
-    if (tid == 0) {  // validation of the best (drl_engine.py:129-171)
-        const double v = pv, tf = bv;
-        double smm = st_smm, sadv = st_sadv;
-        int32_t no_improve = no_improve0;
-        int decayed = 0;
-        if (improved) {
-            st->best_val = v;
-            no_improve = 0;
-        } else {
-            no_improve += 1;
-        }
-        if (no_improve >= patience) {
-            smm *= decay;
-            sadv *= decay;
-            no_improve = 0;
-            decayed = 1;
-        }
-        st->sigma_mm = smm;
-        st->sigma_adv = sadv;
-        st->no_improve = no_improve;
-        st->best_idx = best;
-        st->adv_best_idx = abest;
-        st->last_train_f = tf;
-        st->improved = improved;
-        st->decayed = decayed;
-        st->last_val_f = v;
-        st->gen = gen_i + 1;
-        if (history && gen_i < hist_cap) {
-            sgmm_ga_history* hist = history + gen_i;
-            hist->train_f = tf;
-            hist->train_trades = pt;
-            hist->best_idx = best;
-            hist->val_f = v;
-            hist->val_trades = pvt;
-            hist->sigma_after = smm;
-            hist->flags = improved | (decayed << 1);
-        }
+    if (tid == 0) {  // the tell's record, the validation of the best (drl_engine.py:129-171)
+        sgmm_ga_history* hist = hist_row(history, s.gen, hist_cap);
+        tell_commit(st, hist, best, abest, bv, pt);
+        val_commit(st, hist, s, pv, pvt);
     }
     SGMM_TAIL_STAMP(4, improved);
     SGMM_TAIL_FLUSH;
-    (void)lm;
-    (void)la;
 }
 
-// The tell (tell_only) in a ONE-WAVE workgroup (the path scans above 1024
-// episodes): lane l holds records l, l + 64, ... (loaded 16 at a time, sc1),
-// the wave's argmax is a DPP maximum of the order-preserving key and a DPP
-// minimum of the index among equal keys (np.argmax: first index, NaN first),
-// the best's training record comes from its lane's registers, and the masters
-// are regenerated from up-front loads.  Same results as ga_step_dev.
-constexpr int kWaveRec = 16;     // records per lane loaded together
-constexpr int kWaveChunks = 8;   // float4 master chunks per lane: n <= 2048
+// The tell's argmax and record by ONE WAVE (the last arriver of the lanes and
+// fused scans, wave 0 of the scan workgroups; StepArgs mode kStepArgmax): lane l
+// holds records l, l + 64, ... (loaded 16 at a time, sc1), the wave's argmax is
+// a DPP maximum of the order-preserving key and a DPP minimum of the index among
+// equal keys (np.argmax: first index, NaN first), and the best's training record
+// comes from its lane's registers.  master <- ask(best) follows in the
+// validation launch's tail (regen_master_block).  Same indices and record as
+// ga_step_dev.
+constexpr int kWaveRec = 16;  // records per lane loaded together
 
-__device__ __forceinline__ int wave_min_i32(int v) {
-#define SGMM_MSTEP(CTRL, RM)                                                  \
-    {                                                                         \
-        const int t_ = (int)dpp32<CTRL, RM>((uint32_t)INT32_MAX, (uint32_t)v); \
-        v = t_ < v ? t_ : v;                                                  \
-    }
-    SGMM_MSTEP(0x111, 0xF) SGMM_MSTEP(0x112, 0xF) SGMM_MSTEP(0x114, 0xF)
-    SGMM_MSTEP(0x118, 0xF) SGMM_MSTEP(0x142, 0xA) SGMM_MSTEP(0x143, 0xC)
-#undef SGMM_MSTEP
-    return __builtin_amdgcn_readlane(v, kWave - 1);
-}
-
-// first index of the largest key over the wave (lane candidates (key, idx),
-// idx < 0: none); -1 when no lane has a candidate
-__device__ __forceinline__ int wave_best_index(uint64_t key, int idx) {
-    const uint64_t m = wave_max_u64(idx >= 0 ? key : 0ull);  // valid keys are > 0
-    const int c = wave_min_i32(idx >= 0 && key == m ? idx : INT32_MAX);
-    return c == INT32_MAX ? -1 : c;
-}
-
-__device__ __forceinline__ void regen_master_wave(float* __restrict__ master, int64_t n, float sig, uint64_t seed,
-                                                  uint32_t sid, uint32_t gen, int best) {
-    const int lane = threadIdx.x & (kWave - 1);
-    float m[kWaveChunks][4];
-#pragma unroll
-    for (int j = 0; j < kWaveChunks; ++j) {
-        const int64_t k4 = lane + (int64_t)j * kWave;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) m[j][q] = 4 * k4 + q < n ? master[4 * k4 + q] : 0.0f;
-    }
-#pragma unroll
-    for (int j = 0; j < kWaveChunks; ++j) {
-        const int64_t k4 = lane + (int64_t)j * kWave;
-        if (4 * k4 >= n) break;
-        float z[4];
-        normal4(seed, sid, gen, (uint32_t)best, (uint32_t)k4, z);
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (4 * k4 + q < n) master[4 * k4 + q] = m[j][q] + z[q] * sig;  // ask_row4's arithmetic
-    }
-}
-
-// master <- ask(best) by every thread of the workgroup (4 parameters a thread
-// at a time, each read before it is overwritten): the deferred half of the tell
-__device__ __forceinline__ void regen_master_block(float* __restrict__ master, int64_t n, float sig, uint64_t seed,
-                                                   uint32_t sid, uint32_t gen, int best) {
-    for (int64_t k4 = threadIdx.x; 4 * k4 < n; k4 += blockDim.x) {
-        float m[4], z[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) m[q] = 4 * k4 + q < n ? master[4 * k4 + q] : 0.0f;
-        normal4(seed, sid, gen, (uint32_t)best, (uint32_t)k4, z);
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (4 * k4 + q < n) master[4 * k4 + q] = m[q] + z[q] * sig;  // ask_row4's arithmetic
-    }
-}
-
-// REGEN = false: the argmax and the bookkeeping only; master <- ask(best)
-// happens in the validation launch's tail (regen_master_block)
-template <bool HANDOFF, bool REGEN = true>
+template <bool HANDOFF>
 __device__ void tell_wave(sgmm_ga_state* __restrict__ st, const double* __restrict__ fit,
-                          const int32_t* __restrict__ trades, int32_t P, float* __restrict__ master,
-                          float* __restrict__ master_adv, int64_t n_mm, int64_t n_adv, uint64_t seed,
+                          const int32_t* __restrict__ trades, int32_t P,
                           sgmm_ga_history* __restrict__ history, int32_t hist_cap) {
     const int lane = threadIdx.x & (kWave - 1);
-    const int32_t gen_i = st->gen;
-    const uint32_t gen = (uint32_t)gen_i;
-    const float sig_mm = (float)st->sigma_mm, sig_adv = (float)st->sigma_adv;
+    const int32_t gen = st->gen;
     // this lane's best (ascending indices: the first wins ties) for fit and
     // -fit, over blocks of kWaveRec records per lane, each block's loads issued
     // together
@@ -631,22 +519,7 @@ __device__ void tell_wave(sgmm_ga_state* __restrict__ st, const double* __restri
     const int src = (best < 0 ? 0 : best) & (kWave - 1);
     const double tf = __longlong_as_double((long long)readlane64((uint64_t)__double_as_longlong(bv), src));
     const int32_t ttr = __builtin_amdgcn_readlane(btr, src);
-    // tell (model.py:73-76; drl_engine.py:119-125)
-    if constexpr (REGEN) {
-        regen_master_wave(master, n_mm, sig_mm, seed, 0u, gen, best);
-        if (master_adv) regen_master_wave(master_adv, n_adv, sig_adv, seed, 1u, gen, abest);
-    }
-    if (lane == 0) {
-        st->best_idx = best;
-        st->adv_best_idx = abest;
-        st->last_train_f = tf;
-        if (history && gen_i < hist_cap) {
-            sgmm_ga_history* hist = history + gen_i;
-            hist->train_f = tf;
-            hist->train_trades = ttr;
-            hist->best_idx = best;
-        }
-    }
+    if (lane == 0) tell_commit(st, hist_row(history, gen, hist_cap), best, abest, tf, ttr);
 }
 
 }  // namespace sgmm

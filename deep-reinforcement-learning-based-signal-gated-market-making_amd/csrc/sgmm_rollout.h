@@ -200,6 +200,19 @@ __host__ __device__ __forceinline__ uint32_t kinfo_groups(uint32_t k) { return (
 // its episode's result (agent-scope release, arrival ticket); the last one to
 // arrive acquires, runs the GA step (tell, validation bookkeeping, sigma
 // decay, history) and resets the ticket.  Saves the separate GA launch.
+//
+// StepArgs::mode (the launch plan and its tests pass the integers).  1, the tell
+// with its master regeneration in the scan's tail, is retired: it took a one-wave
+// last arriver ~17 us (profiles/r05_timeline/sc_tr15d.txt); 3 then 4 replace it.
+enum StepMode : int32_t {
+    kStepWhole = 0,     // the whole boundary; records: P training then P validation results per population
+    kStepValidate = 2,  // validation bookkeeping: workgroup k holds population k's post-tell master's record
+    kStepArgmax = 3,    // the tell's argmax and record only (tell_wave)
+    // kStepArgmax's validation launch: episode k rolls out individual best_idx of population k
+    // (GenomeSrc::use_best); workgroup k regenerates the masters, then the bookkeeping
+    kStepDeferred = 4,
+};
+
 struct StepArgs {
     sgmm_ga_state* st;  // nullptr: no GA step in this launch
     float* master_mm;
@@ -216,16 +229,7 @@ struct StepArgs {
     // fitness + k * pop_eps.  pop_eps == 0: one population (the whole grid).
     int32_t pop_eps;
     const uint64_t* seeds;
-    // 0: the whole boundary (records: P training then P validation results per
-    // population); 1: tell only (the validation of the new master follows in its
-    // own launches); 2: validation bookkeeping, one episode per population
-    // (workgroup k = population k's post-tell master, validation_tail);
-    // 3: the tell's argmax only (the last arriver is a one-wave workgroup whose
-    // master regeneration took ~17 us, profiles/r05_timeline/sc_tr15d.txt) and
-    // 4: its validation launch -- episode k rolls out individual best of
-    // population k (GenomeSrc::use_best) and workgroup k regenerates the master
-    // (all its threads) before the bookkeeping
-    int32_t mode;
+    int32_t mode;  // a StepMode
 };
 
 // The episode's fitness record, stored write-through (sc1) by ONE lane of

@@ -492,6 +492,7 @@ extern "C" int sgmm_generation(const sgmm_ticks* ticks, const sgmm_episodes* eps
     step.history = history;
     step.hist_cap = history_cap;
     step.P = P;
+    step.mode = kStepWhole;
     return rollout_impl(plan_knobs(), ticks, eps, params, src, arl, hidden, fitness, trades, workspace,
                         workspace_bytes, step, as_stream(stream));
 }
@@ -528,10 +529,10 @@ static GenomeSrc pops_src(const sgmm_populations* pops, int32_t pop_eps, int32_t
 }
 
 // The generation tail of K populations of P individuals, pop_eps episodes per
-// population in this launch (StepArgs::mode).  Mode 2, the validation
+// population in this launch (StepArgs::mode).  kStepValidate, the validation
 // bookkeeping alone, touches no adversary master.
 static StepArgs pops_step(const sgmm_populations* pops, int32_t P, int32_t pop_eps, int32_t mode) {
-    const bool adv = pops->masters_adv != nullptr && mode != 2;
+    const bool adv = pops->masters_adv != nullptr && mode != kStepValidate;
     StepArgs step{};
     step.st = pops->states;
     step.master_mm = pops->masters_mm;
@@ -562,16 +563,16 @@ extern "C" int sgmm_generation_multi(const sgmm_ticks* ticks, const sgmm_episode
     SGMM_REQUIRE(pops_n_mm(pops) <= kMaxStepParams, "genome too large for the fused GA step");
     return rollout_impl(plan_knobs(), ticks, eps, params, pops_src(pops, 2 * P, 0, false),
                         pops->masters_adv != nullptr, H, fitness, trades, workspace, workspace_bytes,
-                        pops_step(pops, P, 2 * P, 0), as_stream(stream));
+                        pops_step(pops, P, 2 * P, kStepWhole), as_stream(stream));
 }
 
 // Validation of every population's post-tell master (drl_engine.py:129-160):
 // val_eps episode k runs masters_mm row val_eps->genome[k] (= k) with no
 // adversary; the scan's workgroup k then runs population k's validation
 // bookkeeping (validation_tail).  The policy kernel is the table (K episodes).
-// deferred: the training launch's tail ran the tell's argmax only (StepArgs
-// mode 3); episode k rolls out population k's best individual from the
-// pre-tell master and the scan's workgroup k writes the new master (mode 4)
+// deferred: the training launch's tail ran the tell's argmax only
+// (kStepArgmax); episode k rolls out population k's best individual from the
+// pre-tell master and the scan's workgroup k writes the new master (kStepDeferred)
 static int validate_impl(const PlanKnobs& knobs, const sgmm_ticks* ticks, const sgmm_episodes* val_eps,
                          const sgmm_env_params* params, const sgmm_populations* pops, double* val_fitness,
                          int32_t* val_trades, void* workspace, size_t workspace_bytes, hipStream_t s,
@@ -584,7 +585,8 @@ static int validate_impl(const PlanKnobs& knobs, const sgmm_ticks* ticks, const 
     src.mm_stride = pops_n_mm(pops);
     if (deferred) src = pops_src(pops, 1, 0, true);
     return rollout_impl(knobs, ticks, val_eps, params, src, false, H, val_fitness, val_trades, workspace,
-                        workspace_bytes, pops_step(pops, 1, 1, deferred ? 4 : 2), s, nullptr, rj);
+                        workspace_bytes, pops_step(pops, 1, 1, deferred ? kStepDeferred : kStepValidate), s, nullptr,
+                        rj);
 }
 
 extern "C" int sgmm_validate_multi(const sgmm_ticks* ticks, const sgmm_episodes* val_eps,
@@ -629,7 +631,7 @@ extern "C" int sgmm_generation_multi_best(const sgmm_ticks* ticks, const sgmm_ep
     sgmm_episodes tr = *train_eps;
     if (pops->walk_order) tr.order = pops->walk_order;
     if (int rc = rollout_impl(knobs, ticks, &tr, params, pops_src(pops, P, 0, false), pops->masters_adv != nullptr, H,
-                              fitness, trades, workspace, workspace_bytes, pops_step(pops, P, P, 3), s, &job, nullptr,
+                              fitness, trades, workspace, workspace_bytes, pops_step(pops, P, P, kStepArgmax), s, &job, nullptr,
                               pops->walk_order))
         return rc;
     return validate_impl(knobs, ticks, val_eps, params, pops, val_fitness, val_trades, workspace, workspace_bytes, s,

@@ -156,11 +156,8 @@ __device__ __forceinline__ void population_arrive(const StepArgs& sa, const doub
     if (__shfl(last, 0, kWave)) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // compiler order only: loads after the ticket
         sgmm_ga_state* st = sa.st + k;
-        tell_wave<true, false>(st, fitness + (int64_t)k * n_eps, trades + (int64_t)k * n_eps, sa.P,
-                               sa.master_mm + (int64_t)k * sa.n_mm,
-                               sa.master_adv ? sa.master_adv + (int64_t)k * sa.n_adv : nullptr, sa.n_mm, sa.n_adv,
-                               sa.seeds ? sa.seeds[k] : sa.seed,
-                               sa.history ? sa.history + (int64_t)k * sa.hist_cap : nullptr, sa.hist_cap);
+        tell_wave<true>(st, fitness + (int64_t)k * n_eps, trades + (int64_t)k * n_eps, sa.P,
+                        sa.history ? sa.history + (int64_t)k * sa.hist_cap : nullptr, sa.hist_cap);
         if (lane == 0) st->arrivals = 0;
     }
 }

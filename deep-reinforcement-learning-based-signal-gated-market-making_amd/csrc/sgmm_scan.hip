@@ -535,22 +535,16 @@ __device__ __forceinline__ void tail_run(const StepArgs& sa0, const double* fitn
     int* si = reinterpret_cast<int*>(sv + 2 * nt);
     float* lm = reinterpret_cast<float*>(si + 2 * nt);
     float* la = lm + sa.n_mm;
-    const bool tell_only = sa.mode == 1;
-    if (sa.mode == 3) {
-        if (threadIdx.x < kWave)
-            tell_wave<true, false>(sa.st, fitness, trades, sa.P, sa.master_mm, sa.master_adv, sa.n_mm, sa.n_adv,
-                                   sa.seed, sa.history, sa.hist_cap);
-    } else if (tell_only && nt == kWave && sa.n_mm <= 4 * kWave * kWaveChunks && sa.n_adv <= 4 * kWave * kWaveChunks)
-        tell_wave<true>(sa.st, fitness, trades, sa.P, sa.master_mm, sa.master_adv, sa.n_mm, sa.n_adv, sa.seed,
-                        sa.history, sa.hist_cap);
-    else if (sa.P <= nt && sa.n_mm <= 16 * nt && sa.n_adv <= 16 * nt)
+    if (sa.mode == kStepArgmax) {
+        if (threadIdx.x < kWave) tell_wave<true>(sa.st, fitness, trades, sa.P, sa.history, sa.hist_cap);
+    } else if (sa.P <= nt && sa.n_mm <= 16 * nt && sa.n_adv <= 16 * nt)
         ga_step_fused<true>(sa.st, fitness, trades, fitness + sa.P, trades + sa.P, sa.P, sa.master_mm,
                             sa.master_adv, sa.best_master, sa.n_mm, sa.n_adv, sa.seed, sa.history,
-                            sa.hist_cap, sv, si, lm, la, tell_only);
+                            sa.hist_cap, sv, si);
     else
         ga_step_dev<true>(sa.st, fitness, trades, fitness + sa.P, trades + sa.P, sa.P, ShardView{0, 0},
                           sa.master_mm, sa.master_adv, sa.best_master, sa.n_mm, sa.n_adv, sa.seed,
-                          sa.history, sa.hist_cap, nullptr, nullptr, 0, 0, sv, si, lm, la, tell_only);
+                          sa.history, sa.hist_cap, nullptr, nullptr, 0, 0, sv, si, lm, la);
     if (threadIdx.x == 0) sa.st->arrivals = 0;
     SGMM_STAMP(blockIdx.x, 5);
 }
@@ -571,7 +565,7 @@ __device__ __forceinline__ void generation_tail(const StepArgs& sa0, const doubl
 // master and runs its bookkeeping -- no other episode's record is needed.
 __device__ __forceinline__ void validation_tail(const StepArgs& sa, double v, int32_t vtr, int* flag, int k) {
     __syncthreads();  // flag aliases LDS the caller has just read
-    if (sa.mode == 4) {
+    if (sa.mode == kStepDeferred) {
         // the deferred tell: master <- ask(best) with the generation's sigma and
         // counter (the bookkeeping below decays sigma and advances gen)
         const sgmm_ga_state* st = sa.st + k;
@@ -579,8 +573,9 @@ __device__ __forceinline__ void validation_tail(const StepArgs& sa, double v, in
         const int best = st->best_idx, abest = st->adv_best_idx;
         const float smm = (float)st->sigma_mm, sadv = (float)st->sigma_adv;
         const uint64_t seed = sa.seeds ? sa.seeds[k] : sa.seed;
-        regen_master_block(sa.master_mm + (int64_t)k * sa.n_mm, sa.n_mm, smm, seed, 0u, gen, best);
-        if (sa.master_adv) regen_master_block(sa.master_adv + (int64_t)k * sa.n_adv, sa.n_adv, sadv, seed, 1u, gen, abest);
+        regen_master_block(sa.master_mm + (int64_t)k * sa.n_mm, nullptr, sa.n_mm, smm, seed, 0u, gen, best);
+        if (sa.master_adv)
+            regen_master_block(sa.master_adv + (int64_t)k * sa.n_adv, nullptr, sa.n_adv, sadv, seed, 1u, gen, abest);
         __syncthreads();  // the new master before the checkpoint copy reads it
     }
     val_update_dev(sa.st + k, v, vtr, sa.master_mm + (int64_t)k * sa.n_mm,
@@ -729,7 +724,7 @@ __device__ __forceinline__ void scan_episode(int e, int nw, const EpArrays& ep, 
         total = finish_record(params, ep, fitness, trades_out, e, total, tr);
     }
     if (step.st) {
-        if (step.mode == 2 || step.mode == 4) validation_tail(step, total, tr, sh.red, e);
+        if (step.mode == kStepValidate || step.mode == kStepDeferred) validation_tail(step, total, tr, sh.red, e);
         else generation_tail(step, fitness, trades_out, sh.tail, sh.red, e, n_total);
     }
 }

@@ -6,7 +6,8 @@ all-equal populations, neighbours one ulp apart.
 
 (a) sgmm_ga_ask against the Philox / Box-Muller reference;
 (b) the tell through the direct entry points (sgmm_ga_tell, sgmm_ga_step,
-    contiguous and sharded, sgmm_ga_step_multi, sgmm_ga_tell_multi);
+    contiguous and sharded, sgmm_ga_step_multi, sgmm_ga_tell_multi), and the
+    validation bookkeeping alone (sgmm_ga_val_update);
 (c) the same vectors through the tails that run inside the rollout launches,
     injected as idle penalties: an episode whose buy_max / sell_min are NaN never
     fills, so its fitness is exactly 0.0 - params[param[e]].idle_penalty.
@@ -423,6 +424,51 @@ def test_multi_population_boundary(sgmm, P, entry):
                         madv[j], exp[j][1], slots[j] if step else None, slots0[j])
     if not step:
         assert _same(slots, slots0)
+
+
+@pytest.mark.parametrize("use_best", [0, 1])
+def test_val_update_alone(sgmm, use_best):
+    """sgmm_ga_val_update, the validation bookkeeping with no tell before it (the
+    path sgmm_validate_multi's tail shares): _val_value's six cases in sequence on
+    one state with patience 2 -- improvement, no improvement, NaN, -inf, an exact
+    tie with best_val, the decay case -- reading record 0 or record best_idx;
+    state, history (two generations lie past its capacity) and checkpoint slot
+    bit for bit against ga_model.val_update."""
+    from sgmm_amd import _lib
+    L, ptr, s = _lib.load(), _lib.ptr, _lib.stream_ptr()
+    n_rec, best_idx = 5, 3
+    idx = best_idx if use_best else 0
+    model = gm.new_state(sigma=0.1, sigma_adv=0.3, patience=2, decay=0.5)
+    model["best_idx"] = best_idx
+    st = _state_dev(model)
+    hist = torch.zeros((HIST_CAP, 40), dtype=torch.uint8, device=DEV)
+    rows_want = np.zeros(HIST_CAP, _hist_host(hist).dtype)
+    slot = torch.full((G_MM,), 123.0, device=DEV)
+    decays = checkpoints = 0
+    for j in range(6):
+        torch.manual_seed(j)
+        master = torch.randn(G_MM, device=DEV)
+        master0, slot_before = master.clone(), slot.clone()
+        v = _val_value(j, model["best_val"])
+        vf = np.full(n_rec, 1000.0)       # any other record would improve
+        vtr = np.arange(n_rec, dtype=np.int32)
+        vf[idx], vtr[idx] = v, 1000 + j
+        vf_d, vtr_d = _dev(vf), _dev(vtr)
+        _lib.check(L.sgmm_ga_val_update(ptr(st), ptr(vf_d), ptr(vtr_d), use_best, ptr(master), ptr(slot),
+                                        G_MM, ptr(hist), HIST_CAP, s), "sgmm_ga_val_update")
+        gen = int(model["gen"])
+        want = gm.val_update(model, v, 1000 + j)
+        if gen < HIST_CAP:
+            rows_want[gen] = want.row
+        tag = (use_best, j, v)
+        assert gm.same_bits(_state_host(st)[0], want.state), (tag, _state_host(st)[0], want.state)
+        assert gm.same_bits(_hist_host(hist), rows_want), (tag, _hist_host(hist), rows_want)
+        assert _same(master, master0), (tag, "master written")
+        assert _same(slot, master if want.checkpoint else slot_before), (tag, "checkpoint slot", want.checkpoint)
+        model = want.state
+        decays += int(want.state["decayed"])
+        checkpoints += int(want.checkpoint)
+    assert decays >= 1 and checkpoints >= 1
 
 
 # ------------------------------------------------------------------ (c) the in-launch tails
