@@ -194,6 +194,10 @@ SIGNATURES = {
     "sgmm_sgu2_schedule": (ctypes.c_int, [_U64, _I64, _I32, _I32, _VP, _VP, _VP]),
     "sgmm_step_bundle": (ctypes.c_int, [ctypes.POINTER(EventBars), _I32, _VP, _VP, _VP, _I32, _VP, _VP, _VP,
                                         _VP, _VP, _VP]),
+    "sgmm_sgu1_features": (ctypes.c_int, [ctypes.POINTER(EventBars), _I32, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP,
+                                          _VP]),
+    "sgmm_sgu1_forest_bytes": (_SZ, [_I32, _I32]),
+    "sgmm_sgu1_predict": (ctypes.c_int, [_VP, _SZ, _I32, _I32, ctypes.c_float, _VP, _I64, _I64, _VP, _VP, _VP]),
     "sgmm_plan_set": (ctypes.c_int, [_I32, _I32]),
     "sgmm_plan_get": (ctypes.c_int, [_I32]),
     "sgmm_profile_enable": (ctypes.c_int, [ctypes.c_int]),

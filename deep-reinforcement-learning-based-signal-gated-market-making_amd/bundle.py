@@ -11,9 +11,11 @@ libsgmm.so's bundle kernels; all days of a request go in one launch each.
 to what the reference does with pandas before its loops: reading the
 parquet files, the 09:30 filter and the trade_time sort (DataFrame
 .sort_values, so tie order matches).  The signal models stay the caller's:
-m2 receives the windows (scaled by ``scaler``); SGU1's feature table
-(HFTLoader.py:66-135, an xgboost model -- not part of this path) comes from
-the ``sgu1_features`` callable.
+m2 receives the windows (scaled by ``scaler``); m1 receives SGU1's feature
+table (HFTLoader.py:66-126), built on the device by sgmm_sgu1_features -- a
+``gate_units.SGU1Forest`` walks it there for all days in one launch, any
+other m1 gets the reference's DataFrame per day.  A ``sgu1_features``
+callable replaces the device table with the caller's own.
 """
 from __future__ import annotations
 
@@ -85,6 +87,27 @@ class EventBarsGPU:
         self._ws = ws
         self.n_events = self.n_events_dev[:self.n_days].cpu().numpy()
 
+    @classmethod
+    def from_bars(cls, bars, device="cuda"):
+        """Event bars that already exist (a list of per-day dicts of the EV_COLS columns, as
+        day() returns them) placed on the device without the raw streams."""
+        _lib.require_gpu()
+        self = cls.__new__(cls)
+        self.L = _lib.load()
+        dev = self.device = torch.device(device)
+        self.n_days = len(bars)
+        self.n_events = np.array([len(b["trade_time"]) for b in bars], np.int32)
+        self.snap_off = np.concatenate([[0], np.cumsum(self.n_events)]).astype(np.int64)
+        self._in = {"snap_off": torch.from_numpy(self.snap_off).to(dev)}
+        self.cols = {}
+        for c in EV_COLS:
+            dt = np.int64 if c == "trade_time" else np.float64
+            a = np.concatenate([np.asarray(b[c], dt) for b in bars] + [np.zeros(1, dt)])  # never empty
+            self.cols[c] = torch.from_numpy(a).to(dev)
+        self.n_events_dev = torch.from_numpy(np.concatenate([self.n_events, np.zeros(1, np.int32)])).to(dev)
+        self.bars = EventBars(ptr(self.n_events_dev), *[ptr(self.cols[k]) for k in EV_COLS])
+        return self
+
     def day(self, d: int) -> dict:
         """Event bars of day d as host arrays (HFTMarketBase.event_df columns)."""
         a, n = int(self.snap_off[d]), int(self.n_events[d])
@@ -110,6 +133,44 @@ class EventBarsGPU:
         self.X_all, self.win_off, self.n_windows = X, win_off, nw
         return [(X[win_off[d]:win_off[d] + nw[d]].unsqueeze(-1), y[win_off[d]:win_off[d] + nw[d]])
                 for d in range(self.n_days)]
+
+    def sgu1_table(self):
+        """SGU1DataPro.gen_dataset(19) of every day in one launch: list of per-day device
+        views (X [20, n] float32 -- xgboost's matrix, feature-major --, label [n] float64).
+        The whole matrix stays in ``sgu1_X`` ([20, sgu1_ld], rows of day d from
+        sgu1_row_off[d]), the table before the float32 cast in ``sgu1_F64``."""
+        from .gate_units import SGU1_FEATURES
+        bars = np.maximum(self.n_events.astype(np.int64) - 1, 0) // EVENT_STEP  # len(range(0, n - 19, 19))
+        row_off = np.concatenate([[0], np.cumsum(bars)]).astype(np.int64)  # one row per bar: no gaps to predict
+        dev, nf, ld = self.device, len(SGU1_FEATURES), max(int(row_off[-1]), 1)
+        X = torch.zeros((nf, ld), dtype=torch.float32, device=dev)
+        F64 = torch.zeros((nf, ld), dtype=torch.float64, device=dev)
+        label = torch.zeros(ld, dtype=torch.float64, device=dev)
+        nr = torch.zeros(max(self.n_days, 1), dtype=torch.int32, device=dev)
+        bars_max = int(bars.max()) if self.n_days else 0
+        row_off_d = torch.from_numpy(row_off).to(dev)  # held until the launch is enqueued
+        check(self.L.sgmm_sgu1_features(ctypes.byref(self.bars), self.n_days, ptr(self._in["snap_off"]),
+                                        ptr(row_off_d), bars_max, ld, ptr(X), ptr(label), ptr(F64), ptr(nr),
+                                        stream_ptr()), "sgmm_sgu1_features")
+        nr = nr[:self.n_days].cpu().numpy()
+        if (nr < 0).any():
+            raise _lib.SgmmError(f"more than 4096 bars on day(s) {np.nonzero(nr < 0)[0].tolist()}")
+        self.sgu1_X, self.sgu1_F64, self.sgu1_label = X, F64, label
+        self.sgu1_ld, self.sgu1_row_off, self.sgu1_n_rows = ld, row_off, nr
+        return [(X[:, row_off[d]:row_off[d] + nr[d]], label[row_off[d]:row_off[d] + nr[d]])
+                for d in range(self.n_days)]
+
+    def sgu1_frame(self, d: int):
+        """The reference's DataFrame of day d (after sgu1_table()): the 20 feature columns
+        and 'label' in float64, f_hour int64."""
+        import pandas as pd
+        from .gate_units import SGU1_FEATURES
+        a, n = int(self.sgu1_row_off[d]), int(self.sgu1_n_rows[d])
+        tab = self.sgu1_F64[:, a:a + n].cpu().numpy()
+        df = pd.DataFrame({c: tab[f] for f, c in enumerate(SGU1_FEATURES)})
+        df["f_hour"] = df["f_hour"].astype(np.int64)
+        df["label"] = self.sgu1_label[a:a + n].cpu().numpy()
+        return df
 
     def steps(self, n_samples) -> tuple:
         """The step loop of load_signals_bundle for every day with its number of
@@ -150,16 +211,17 @@ def _fused_sgu2(m2, scaler) -> bool:
 def load_signals_bundle(symbol, date_list, m1, m2, scaler, *, sgu1_features=None, data_root=".",
                         device="cuda"):
     """pipeline/agent_trainer.py:15-78 with the event bars, the SGU2 windows
-    and the step loop on the GPU.  ``sgu1_features(event_bars_dict)`` must
-    return SGU1DataPro.gen_dataset(19)'s table (with its 'label' column) for
-    one day's event bars.  With this package's SGU2 as m2 and a float32
+    the SGU1 feature table and the step loop on the GPU.  With a
+    gate_units.SGU1Forest as m1 every day's rows go through one forest launch;
+    any other m1 gets ``m1.predict(table.drop(columns=['label']))`` per day as
+    in the reference.  A ``sgu1_features(event_bars_dict)`` callable, when
+    passed, supplies SGU1DataPro.gen_dataset(19)'s table (with its 'label'
+    column) for one day's event bars instead.  With this package's SGU2 as m2 and a float32
     StandardScaler3D, SGU2 runs on the device windows of all days at once
     (gate_units.SGU2.predict_device); any other m2 / scaler gets the host
     windows as in the reference."""
     import pandas as pd
-    if sgu1_features is None:
-        raise NotImplementedError("SGU1's feature table (HFTLoader.py:66-135, an xgboost input) is not "
-                                  "part of this path: pass sgu1_features=callable(event_bars_dict)")
+    from .gate_units import SGU1Forest
     snap_dir = os.path.join(data_root, "data", symbol, "snap")
     tick_dir = os.path.join(data_root, "data", symbol, "tick")
     days, kept = [], []
@@ -176,14 +238,25 @@ def load_signals_bundle(symbol, date_list, m1, m2, scaler, *, sgu1_features=None
     s2_all = None
     if _fused_sgu2(m2, scaler):  # every day's windows through SGU2 in one launch, scaled in the kernel
         s2_all = m2.predict_device(ev.X_all, scaler).cpu().numpy()
+    s1_all = None
+    if sgu1_features is None:
+        ev.sgu1_table()
+        if isinstance(m1, SGU1Forest):  # every day's rows through the forest in one launch
+            s1_all = m1.predict_device(ev.sgu1_X, ev.sgu1_ld, ev.sgu1_ld).cpu().numpy()
     s1s, s2s, n_samples, used = [], [], [], []
     for k in range(len(days)):
-        df1 = sgu1_features(ev.day(k))
+        df1 = sgu1_features(ev.day(k)) if sgu1_features is not None else None
+        n1 = len(df1) if df1 is not None else int(ev.sgu1_n_rows[k])
         n_win = int(ev.n_windows[k])
-        if len(df1) == 0 or n_win == 0:
+        if n1 == 0 or n_win == 0:
             n_samples.append(0)
             continue
-        s1 = np.asarray(m1.predict(df1.drop(columns=["label"])))
+        if s1_all is not None:
+            s1 = s1_all[ev.sgu1_row_off[k]:ev.sgu1_row_off[k] + n1]
+        else:
+            if df1 is None:
+                df1 = ev.sgu1_frame(k)
+            s1 = np.asarray(m1.predict(df1.drop(columns=["label"])))
         if s2_all is not None:
             s2 = s2_all[ev.win_off[k]:ev.win_off[k] + n_win]
         else:

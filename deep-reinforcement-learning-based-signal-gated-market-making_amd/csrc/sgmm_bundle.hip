@@ -25,12 +25,11 @@
 // the compactions, no matrix cores.
 #include <cmath>
 
+#include "sgmm_bars_device.h"
 #include "sgmm_device.h"
 #include "sgmm_internal.h"
 
 namespace sgmm {
-
-constexpr int kDayBlock = 1024;
 
 // exclusive block scan of one 0/1 flag per thread; returns the prefix and
 // writes the block total to *total (all threads)
@@ -152,48 +151,7 @@ __global__ __launch_bounds__(kDayBlock) void k_event_bars(sgmm_day_streams in, s
     if (tid == 0) out.n_events[d] = ne;
 }
 
-constexpr int kEventStep = 19, kTimeSteps = 10;
-constexpr int kMaxBars = 4096;  // bars per day held in LDS (4096 * 19 events)
-
-// pandas' Series.mean of 19 quotes (nanops.nanmean, skipna): NaN counts as 0
-// in numpy's float64 add.reduce order for n in [8, 128) -- 8 strided
-// accumulators, combined pairwise, then the tail in order -- and the sum is
-// divided by the number of non-NaN quotes; NaN when there is none.  A call,
-// not inlined: with both means inlined k_bar_windows holds 38 quotes at once
-// and spills at the 128 VGPRs a 1024-thread block leaves it (66 and none so)
-__device__ __noinline__ double skipna_mean_19(const double* a) {
-    int count = 0;
-    auto q = [&](int j) -> double {
-        const double x = a[j];
-        const bool ok = x == x;
-        count += ok ? 1 : 0;
-        return ok ? x : 0.0;
-    };
-    double r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = q(j);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = r[j] + q(8 + j);
-    double s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    s = s + q(16);
-    s = s + q(17);
-    s = s + q(18);
-    return count > 0 ? s / count : NAN;
-}
-
-__device__ __forceinline__ double nan_max_run(const double* a, int n) {
-    double m = NAN;
-    for (int i = 0; i < n; ++i)
-        if (a[i] == a[i]) m = (m != m || a[i] > m) ? a[i] : m;
-    return m;
-}
-
-__device__ __forceinline__ double nan_min_run(const double* a, int n) {
-    double m = NAN;
-    for (int i = 0; i < n; ++i)
-        if (a[i] == a[i]) m = (m != m || a[i] < m) ? a[i] : m;
-    return m;
-}
+constexpr int kTimeSteps = 10;
 
 // SGU2DataPro.gen_dataset (HFTLoader.py:139-169) per day: X[w][k] = return
 // k of window w (float32), y[w]; n_windows[d] = max(0, bars - 11)

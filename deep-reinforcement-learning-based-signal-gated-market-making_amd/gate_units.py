@@ -21,8 +21,14 @@ dropout streams are not reproduced.  The reference's ``best_state`` aliases
 the live parameters, so its final ``load_state_dict(best_state)`` restores
 nothing and the model ends with the last epoch's weights:
 ``restore_best=False`` (the default) reproduces that, ``restore_best=True``
-restores a real snapshot taken on the device after the best epoch.  SGU1
-(xgboost) stays on the host; the scaler fit stays on the host too.
+restores a real snapshot taken on the device after the best epoch.  The
+scaler fit stays on the host.
+
+``SGU1Forest`` is SGU1's inference side (GateUnits.py:7-40, an
+xgboost.XGBRegressor): it reads xgboost's JSON model, packs the trees on the
+host and runs sgmm_sgu1_predict over the device feature table of
+``EventBarsGPU.sgu1_table`` (or any [n, 20] rows).  SGU1 *training* stays
+with xgboost on the host.
 """
 from __future__ import annotations
 
@@ -334,3 +340,175 @@ def train_sgu2_many(models, X_train, y_train, X_val, y_val, batch_size=128, epoc
             histories[k] = {"train_loss": [float(v) for v in out["train_loss"][i][:ran]],
                             "val_loss": [float(v) for v in out["val_loss"][i][:ran]]}
     return histories
+
+
+# ----------------------------------------------------------------- SGU1 inference (sgmm_sgu1_predict)
+SGU1_FEATURES = tuple([f"f_trades_{p}" for p in (1, 2, 3, 5, 10)] + [f"f_vwap_{r}" for r in (1, 3, 5)] +
+                      [f"f_slope_{s}" for s in (1, 3, 5)] + [f"f_lag_rr_{k}" for k in (1, 2, 3, 4, 5)] +
+                      ["f_spread", "f_vol_imb", "f_total_vol", "f_hour"])
+MAX_FOREST_DEPTH = 6
+
+
+def pack_forest(left, right, feat, value, default_left, tree_off):
+    """Node arrays of a forest (tree t owns nodes tree_off[t] .. tree_off[t+1]; children are
+    tree-local, -1 at a leaf; value is the threshold of a split and the weight of a leaf) ->
+    (depth, blob): every tree as a complete binary tree of the forest's depth in the layout of
+    sgmm_sgu1_forest_bytes (include/sgmm.h), a leaf above that depth filling its subtree.
+    Raises ValueError for children out of range, features outside the 20 columns and walks
+    that do not end within depth 6 (deeper trees, cycles).  The filler splits below a shallow
+    leaf carry a NaN threshold and no default-left bit: every row goes right there, so such a
+    leaf is reported at the rightmost position of its subtree."""
+    left, right = np.asarray(left, np.int64).ravel(), np.asarray(right, np.int64).ravel()
+    feat, dl = np.asarray(feat, np.int64).ravel(), np.asarray(default_left).ravel().astype(bool)
+    value, off = np.asarray(value, np.float32).ravel(), np.asarray(tree_off, np.int64).ravel()
+    T, N = len(off) - 1, len(left)
+    if T < 0 or off[0] != 0 or off[-1] != N or (np.diff(off) < 1).any() or not (
+            len(right) == len(feat) == len(dl) == len(value) == N):
+        raise ValueError("forest arrays disagree in length, or a tree without nodes")
+    size = np.repeat(np.diff(off), np.diff(off))
+    leaf = left == -1
+    if ((right == -1) != leaf).any() or ((~leaf) & ((left < 0) | (left >= size) | (right < 0) | (right >= size))).any():
+        raise ValueError("child index outside its tree")
+    if ((~leaf) & ((feat < 0) | (feat >= len(SGU1_FEATURES)))).any():
+        raise ValueError(f"split feature outside the {len(SGU1_FEATURES)} columns")
+    base = np.repeat(off[:-1], np.diff(off))
+    lg, rg = np.where(leaf, np.arange(N), left + base), np.where(leaf, np.arange(N), right + base)
+    levels = [off[:-1].reshape(T, 1)]  # node behind every position of the complete tree, level by level
+    while not leaf[levels[-1]].all():
+        if len(levels) > MAX_FOREST_DEPTH:
+            raise ValueError(f"a walk does not end within depth {MAX_FOREST_DEPTH}")
+        cur = levels[-1]
+        levels.append(np.stack([lg[cur], rg[cur]], axis=-1).reshape(T, -1))
+    while len(levels) < 2:  # a forest of single leaves: one filler split whose sides agree
+        levels.append(np.repeat(levels[-1], 2, axis=1))
+    D = len(levels) - 1
+    inner = np.concatenate(levels[:-1], axis=1)  # [T, 2^D - 1], level order
+    blob = np.zeros((T, 3 * (1 << D) - 2), np.uint32)
+    split = ~leaf[inner]
+    blob[:, 0:2 * inner.shape[1]:2] = np.where(split, value[inner], np.float32(np.nan)).astype(np.float32).view(np.uint32)
+    blob[:, 1:2 * inner.shape[1]:2] = np.where(split, feat[inner] | (dl[inner].astype(np.int64) << 31), 0)
+    blob[:, 2 * inner.shape[1]:] = value[levels[-1]].view(np.uint32)
+    return D, blob
+
+
+class SGU1Forest:
+    """SGU1 inference (GateUnits.py:7-40's XGBRegressor.predict) on the device:
+    a gbtree model of reg:squarederror read from xgboost's JSON, packed into
+    complete trees and walked by sgmm_sgu1_predict.  predict() uses the first
+    best_iteration + 1 trees when the model carries that attribute, as
+    XGBRegressor.predict does after early stopping (``n_trees`` overrides)."""
+
+    feature_names = SGU1_FEATURES
+
+    def __init__(self, model_path=None):
+        self.model_path = model_path
+        self.left = self.right = self.feat = self.value = self.default_left = self.tree_off = None
+        self.base_score = np.float32(0.5)
+        self.best_iteration = None
+        self.n_trees = 0
+        self.depth, self._blob, self._dev = 0, None, {}
+        if model_path is not None:
+            self.load(model_path)
+
+    @classmethod
+    def from_arrays(cls, left, right, feat, value, default_left, tree_off, base_score, best_iteration=None):
+        self = cls()
+        self.left, self.right = np.asarray(left, np.int32).ravel(), np.asarray(right, np.int32).ravel()
+        self.feat, self.value = np.asarray(feat, np.int32).ravel(), np.asarray(value, np.float32).ravel()
+        self.default_left = np.asarray(default_left).ravel().astype(np.uint8)
+        self.tree_off = np.asarray(tree_off, np.int64).ravel()
+        self.base_score = np.float32(base_score)
+        total = len(self.tree_off) - 1
+        self.best_iteration = None if best_iteration is None or int(best_iteration) < 0 else int(best_iteration)
+        self.n_trees = total if self.best_iteration is None else min(self.best_iteration + 1, total)
+        self.depth, self._blob = pack_forest(self.left, self.right, self.feat, self.value, self.default_left,
+                                             self.tree_off)
+        self._dev = {}
+        return self
+
+    def load(self, path):
+        """xgboost's JSON model (Booster.save_model / XGBRegressor.save_model)."""
+        import json
+        with open(path) as fh:
+            learner = json.load(fh)["learner"]
+        booster = learner["gradient_booster"]
+        if booster.get("name") != "gbtree":
+            raise ValueError(f"booster {booster.get('name')!r}: only gbtree is supported")
+        if learner["objective"]["name"] != "reg:squarederror":
+            raise ValueError(f"objective {learner['objective']['name']!r}: only reg:squarederror is supported")
+        par = learner["learner_model_param"]
+        if int(par.get("num_target", "1")) != 1 or int(par.get("num_class", "0")) > 1:
+            raise ValueError("only one target is supported")
+        if int(par["num_feature"]) != len(SGU1_FEATURES):
+            raise ValueError(f"model of {par['num_feature']} features: SGU1 has {len(SGU1_FEATURES)}")
+        names = learner.get("feature_names") or list(SGU1_FEATURES)
+        if tuple(names) != SGU1_FEATURES:
+            raise ValueError("feature_names differ from SGU1DataPro.gen_dataset's columns")
+        model = booster["model"]
+        if int(model["gbtree_model_param"].get("num_parallel_tree", "1")) != 1:
+            raise ValueError("num_parallel_tree != 1")
+        trees = model["trees"]
+        for t in trees:
+            if any(int(s) != 0 for s in t.get("split_type", [])) or len(t.get("categories", [])):
+                raise ValueError("categorical splits are not supported")
+            if int(t["tree_param"].get("size_leaf_vector", "1")) > 1:
+                raise ValueError("vector leaves are not supported")
+        cat = lambda k, dt: np.concatenate([np.asarray(t[k], dt) for t in trees]) if trees else np.zeros(0, dt)
+        best = learner.get("attributes", {}).get("best_iteration")
+        other = self.from_arrays(cat("left_children", np.int32), cat("right_children", np.int32),
+                                 cat("split_indices", np.int32), cat("split_conditions", np.float32),
+                                 cat("default_left", np.uint8),
+                                 np.concatenate([[0], np.cumsum([len(t["left_children"]) for t in trees])]),
+                                 np.float32(str(par["base_score"]).strip("[] ")), None if best is None else int(best))
+        self.__dict__.update(other.__dict__)
+        self.model_path = path
+        return self
+
+    def _device_blob(self, dev):
+        key = str(dev)
+        if key not in self._dev:
+            self._dev = {key: torch.from_numpy(self._blob.view(np.int32).reshape(-1).copy()).to(dev)}
+        return self._dev[key]
+
+    def predict_device(self, X: torch.Tensor, ld: int, n: int, *, n_trees=None, leaves=False):
+        """X: the float32 feature-major matrix [20 * ld] on the device (sgmm_sgu1_features'
+        layout) -> float32 [n] (and int32 leaf positions [n, n_trees] with leaves=True)."""
+        _lib.require_gpu()
+        L = _lib.load()
+        if self._blob is None:
+            raise ValueError("SGU1Forest holds no model")
+        if X.dtype != torch.float32 or X.device.type != "cuda" or not X.is_contiguous():
+            raise TypeError("predict_device needs a contiguous float32 matrix on the device")
+        nt = self.n_trees if n_trees is None else int(n_trees)
+        if not 0 <= nt <= len(self.tree_off) - 1 or not 0 <= n <= ld or X.numel() < len(SGU1_FEATURES) * ld:
+            raise ValueError("n_trees, n or ld out of range")
+        dev = X.device
+        blob = self._device_blob(dev)
+        out = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+        lv = torch.empty((max(n, 1), max(nt, 1)), dtype=torch.int32, device=dev) if leaves else None
+        check(L.sgmm_sgu1_predict(ptr(blob), blob.numel() * 4, self.depth, nt, float(self.base_score), ptr(X), ld, n,
+                                  ptr(out), ptr(lv), stream_ptr()), "sgmm_sgu1_predict")
+        return (out[:n], lv[:n, :nt]) if leaves else out[:n]
+
+    def _matrix(self, X):
+        """DataFrame / array [n, 20] -> xgboost's float32 matrix, feature-major on the device."""
+        if hasattr(X, "columns"):
+            if tuple(X.columns) != SGU1_FEATURES:
+                raise ValueError("columns differ from SGU1DataPro.gen_dataset's")
+            X = X.to_numpy(dtype=np.float64)
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape[1] != len(SGU1_FEATURES):
+            raise ValueError(f"SGU1 rows carry {len(SGU1_FEATURES)} features")
+        n = X.shape[0]
+        Xt = np.ascontiguousarray(X.astype(np.float32).T).reshape(-1) if n else np.zeros(len(SGU1_FEATURES), np.float32)
+        return torch.from_numpy(Xt).to("cuda"), max(n, 1), n
+
+    def predict(self, X, n_trees=None):
+        Xd, ld, n = self._matrix(X)
+        return self.predict_device(Xd, ld, n, n_trees=n_trees).cpu().numpy()
+
+    def pred_leaf(self, X, n_trees=None):
+        """Position 0 .. 2^depth - 1 of the leaf every tree ends in (in the packed complete
+        tree; the analogue of Booster.predict(pred_leaf=True)'s node ids): int32 [n, n_trees]."""
+        Xd, ld, n = self._matrix(X)
+        return self.predict_device(Xd, ld, n, n_trees=n_trees, leaves=True)[1].cpu().numpy()

@@ -2,7 +2,9 @@
 inference on the GPU (gate_units.py, sgmm_sgu2_forward) with the reference's
 checkpoint format; SGU1 stays the host xgboost regressor it is in the
 reference (GateUnits.py:7-40), built lazily so that importing this module does
-not need xgboost until an SGU1 is constructed."""
+not need xgboost until an SGU1 is constructed.  SGU1Forest is its inference
+side without xgboost: it loads the JSON model SGU1.save wrote and predicts on
+the GPU (gate_units.SGU1Forest, sgmm_sgu1_predict)."""
 import os
 import sys
 
@@ -12,6 +14,7 @@ from sgmm_amd import gate_units as _gu  # noqa: E402
 
 SGU2 = _gu.SGU2
 SGU2Model = _gu.SGU2Model
+SGU1Forest = _gu.SGU1Forest
 
 
 class SGU1:

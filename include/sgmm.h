@@ -661,6 +661,46 @@ int sgmm_step_bundle(const sgmm_event_bars *ev, int32_t n_days, const int64_t *s
                      void *stream);
 
 /* ------------------------------------------------------------------------
+ * SGU1: the feature table and boosted-tree inference
+ * ------------------------------------------------------------------------ */
+
+/* SGU1DataPro.gen_dataset(event_step=19) (HFTLoader.py:66-126) for every day,
+ * one workgroup per day.  Rows of day d are row_off[d] .. +n_rows[d] (the
+ * caller leaves room for one row per bar); n_rows[d] is the day's bar count,
+ * 0 below 6 bars, -1 above 4096 bars (nothing is written then).  X is the
+ * float32 matrix xgboost builds from the table, feature-major: feature f of
+ * row r at X[f * ld + r], f in the order f_trades_{1,2,3,5,10},
+ * f_vwap_{1,3,5}, f_slope_{1,3,5}, f_lag_rr_{1..5}, f_spread, f_vol_imb,
+ * f_total_vol, f_hour.  label[ld]: the float64 label column.  F64[20 * ld]:
+ * the table before the cast, same layout, or NULL.  Domain: positive finite
+ * quotes (NaN trade statistics are inside it).  The rolling means are pandas'
+ * sliding Kahan means bit for bit; the slopes are closed forms within
+ * 4 * 2^-52 * max|mid| of the exact least-squares slope (np.polyfit is not
+ * reproduced bit for bit; a flat window gives exactly +0.0). */
+int sgmm_sgu1_features(const sgmm_event_bars *ev, int32_t n_days, const int64_t *snap_off,
+                       const int64_t *row_off, int64_t max_bars_per_day, int64_t ld, float *X,
+                       double *label, double *F64, int32_t *n_rows, void *stream);
+
+/* Bytes of a packed forest: n_trees complete binary trees of `depth`
+ * (1..6, else 0), each 2^depth - 1 internal nodes in level order (children of
+ * k: 2k+1 left, 2k+2 right) of { float thr; uint32 word } -- word bits 0-4 the
+ * feature, bit 31 set when a NaN feature goes left -- followed by 2^depth
+ * float leaves, left to right.  A leaf above `depth` fills its whole subtree. */
+size_t sgmm_sgu1_forest_bytes(int32_t depth, int32_t n_trees);
+
+/* xgboost's CPU predictor for reg:squarederror over a packed forest in device
+ * memory (16-byte aligned): out[r] = base_score, then += the leaf of tree
+ * 0, 1, ... n_trees-1 in float32, in that order; at a node x[feat] < thr goes
+ * left, otherwise right, NaN the default side.  X as sgmm_sgu1_features
+ * writes it (20 features, ld >= n_rows).  leaves[n_rows, n_trees]: position
+ * 0 .. 2^depth - 1 of the leaf each tree ends in, or NULL.  The kernel masks
+ * the feature to 5 bits over a 32-column staging, so no blob content indexes
+ * out of bounds.  depth > 6: SGMM_ERR_UNSUPPORTED. */
+int sgmm_sgu1_predict(const void *forest_blob, size_t blob_bytes, int32_t depth, int32_t n_trees,
+                      float base_score, const float *X, int64_t ld, int64_t n_rows, float *out,
+                      int32_t *leaves, void *stream);
+
+/* ------------------------------------------------------------------------
  * SGU2 inference
  * ------------------------------------------------------------------------ */
 

@@ -17,6 +17,11 @@ Algorithmic bytes / flops per launch (DESIGN.md "Bundle builder"):
   step_bundle  20 rows x 16 B (p_buy_max, p_sell_min) + 32 B read, 40 B
                written per step
   sgu2         per window and step 2*4H(H+1) + 6H FLOP (H = 10: 940), 40 B read
+  sgu1_features 72 B per event read (9 columns), 20 x 12 + 8 B per row written
+               (float32 matrix, float64 table, label)
+  sgu1_forest  per row and tree D node reads (8 B), D feature reads (4 B) and one
+               leaf read (4 B) from LDS, each depending on the one before:
+               2 D + 1 dependent LDS reads (D = 4, 581 trees: 5 229 per row)
 """
 from __future__ import annotations
 
@@ -137,6 +142,40 @@ def main():
                   "value": nwin / sec, "us_per_launch": sec * 1e6,
                   "roofline": {"bound": "valu", "achieved": flop / sec / 1e12, "peak": FP32_PEAK_TFLOPS,
                                "unit": "TFLOP/s", "frac": flop / sec / 1e12 / FP32_PEAK_TFLOPS, "flop": flop}})
+    # SGU1: the feature table of the same year of days, and the 688981-sized forest (581 of 601
+    # depth-4 trees, random splits over the table's own value ranges) on the table's rows
+    from sgmm_amd.gate_units import SGU1Forest
+    ev.sgu1_table()
+    R = int(ev.sgu1_n_rows.sum())
+    sec, _ = timed(ev.sgu1_table, args.reps, "sgu1_features")
+    byt = 72 * E + 248 * R
+    lines.append({"kernel": "k_sgu1_features", "workload": f"{args.days} days, {R} rows", "unit_rate": "rows/s",
+                  "value": R / sec, "us_per_launch": sec * 1e6,
+                  "roofline": {"bound": "latency", "note": "one workgroup per day; the two rolling-mean chains are "
+                               "serial over the day's bars (one lane each)", "hbm_GBps": byt / sec / 1e9,
+                               "algorithmic_bytes": byt}})
+    rng = np.random.default_rng(1)
+    Xh = ev.sgu1_X.cpu().numpy()
+    lo, hi = Xh.min(axis=1), Xh.max(axis=1)
+    D, NT, USE = 4, 601, 581
+    left = np.tile(np.r_[2 * np.arange(15) + 1, np.full(16, -1)], NT)
+    right = np.tile(np.r_[2 * np.arange(15) + 2, np.full(16, -1)], NT)
+    feat = rng.integers(0, 20, 31 * NT)
+    value = np.where(left >= 0, lo[feat] + rng.random(31 * NT) * (hi[feat] - lo[feat]), rng.normal(0, 0.1, 31 * NT))
+    forest = SGU1Forest.from_arrays(left, right, feat, value, rng.integers(0, 2, 31 * NT), 31 * np.arange(NT + 1),
+                                    46.69237, USE - 1)
+    ld = ev.sgu1_ld
+    sec, _ = timed(lambda: forest.predict_device(ev.sgu1_X, ld, ld), args.reps, "sgu1_forest")
+    reads = (2 * D + 1) * USE
+    rounds = -(-(-(-ld // 256)) // 256)  # 256-row workgroups, one per CU at a time (152 KiB of LDS each)
+    lds_cyc = rounds * 4 * USE * (2 * D * 2 + 2)  # per CU: ds_read_b64 / _b32 take 2 LDS cycles per wave-instruction
+    lines.append({"kernel": "k_sgu1_forest<4>", "workload": f"{ld} rows x {USE} trees of depth {D}",
+                  "unit_rate": "rows/s", "value": ld / sec, "us_per_launch": sec * 1e6,
+                  "dependent_lds_reads_per_row": reads, "workgroup_rounds": rounds,
+                  "ns_per_tree": sec * 1e9 / rounds / USE,
+                  "roofline": {"bound": "lds-latency", "note": "per CU one workgroup of 4 waves, 16 trees in flight "
+                               "per wave; LDS issue floor = conflict-free reads at 2 cycles per wave-instruction",
+                               "lds_cycles_per_cu": lds_cyc, "frac_of_lds_issue_at_2.4GHz": lds_cyc / 2.4e9 / sec}})
     # the recorder's trace launch: 64 backtests (checkpoints x phi sweep) of one 960-step test bundle
     b = bundle_510300(960, seed=4)
     ts = TickStore()
