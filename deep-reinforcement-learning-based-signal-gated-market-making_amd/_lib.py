@@ -120,7 +120,21 @@ class Sgu2Task(ctypes.Structure):
         [("n", ctypes.c_int64), ("nv", ctypes.c_int64), ("seed", ctypes.c_uint64), ("lr", ctypes.c_double)]
 
 
+class Sgu1Task(ctypes.Structure):
+    """sgmm_sgu1_task: one SGU1 fit (device pointers, see include/sgmm.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("X_train", "y_train", "rows_train", "X_val", "y_val", "rows_val", "cuts",
+                                               "n_cuts", "workspace", "left", "right", "feature", "value",
+                                               "default_left", "base_weight", "loss_change", "sum_hessian",
+                                               "tree_nodes", "val_rmse", "n_trees", "best_iteration", "best_score")] + \
+        [("ld_train", ctypes.c_int64), ("ld_val", ctypes.c_int64)] + \
+        [(n, ctypes.c_int32) for n in ("n_train", "n_val", "max_depth", "n_estimators", "early_stopping_rounds",
+                                       "max_bin")] + \
+        [("base_score", ctypes.c_float), ("reserved", ctypes.c_float)] + \
+        [(n, ctypes.c_double) for n in ("min_child_weight", "eta", "lambda_", "alpha", "gamma")]
+
+
 assert ctypes.sizeof(EnvParams) == 48
+assert ctypes.sizeof(Sgu1Task) == 264
 assert ctypes.sizeof(Sgu2Task) == 128
 assert ctypes.sizeof(DMResult) == 40
 assert ctypes.sizeof(MBBResult) == 40
@@ -192,6 +206,8 @@ SIGNATURES = {
     "sgmm_sgu2_loss_grad": (ctypes.c_int, [_VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP, ctypes.c_float, _VP, _VP,
                                            _VP, _SZ, _VP]),
     "sgmm_sgu2_schedule": (ctypes.c_int, [_U64, _I64, _I32, _I32, _VP, _VP, _VP]),
+    "sgmm_sgu1_train_workspace_bytes": (_SZ, [_I64, _I64]),
+    "sgmm_sgu1_train": (ctypes.c_int, [_VP, ctypes.POINTER(Sgu1Task), _I32, _VP]),
     "sgmm_step_bundle": (ctypes.c_int, [ctypes.POINTER(EventBars), _I32, _VP, _VP, _VP, _I32, _VP, _VP, _VP,
                                         _VP, _VP, _VP]),
     "sgmm_sgu1_features": (ctypes.c_int, [ctypes.POINTER(EventBars), _I32, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP,

@@ -17,7 +17,8 @@ from pathlib import Path
 PKG_DIR = Path(__file__).resolve().parent
 SOURCES = ["csrc/sgmm_capi.hip", "csrc/sgmm_rollout.hip", "csrc/sgmm_scan.hip", "csrc/sgmm_table.hip",
            "csrc/sgmm_frontier.hip", "csrc/sgmm_ga.hip", "csrc/sgmm_bundle.hip", "csrc/sgmm_sgu2.hip",
-           "csrc/sgmm_evaluate.hip", "csrc/sgmm_hypothesis.hip", "csrc/sgmm_sgu2_train.hip", "csrc/sgmm_sgu1.hip"]
+           "csrc/sgmm_evaluate.hip", "csrc/sgmm_hypothesis.hip", "csrc/sgmm_sgu2_train.hip", "csrc/sgmm_sgu1.hip",
+           "csrc/sgmm_sgu1_train.hip"]
 HEADERS = ["csrc/sgmm_device.h", "csrc/sgmm_internal.h", "csrc/sgmm_ga_device.h", "csrc/sgmm_rollout.h",
            "csrc/sgmm_mlp_mfma.h", "csrc/sgmm_scan.h", "csrc/sgmm_plan.h", "csrc/sgmm_sgu2_device.h",
            "csrc/sgmm_bars_device.h",

@@ -212,8 +212,8 @@ def load_signals_bundle(symbol, date_list, m1, m2, scaler, *, sgu1_features=None
                         device="cuda"):
     """pipeline/agent_trainer.py:15-78 with the event bars, the SGU2 windows
     the SGU1 feature table and the step loop on the GPU.  With a
-    gate_units.SGU1Forest as m1 every day's rows go through one forest launch;
-    any other m1 gets ``m1.predict(table.drop(columns=['label']))`` per day as
+    gate_units.SGU1Forest as m1 (or a gate_units.SGU1, which holds one after a
+    fit or a load) every day's rows go through one forest launch; any other m1 gets ``m1.predict(table.drop(columns=['label']))`` per day as
     in the reference.  A ``sgu1_features(event_bars_dict)`` callable, when
     passed, supplies SGU1DataPro.gen_dataset(19)'s table (with its 'label'
     column) for one day's event bars instead.  With this package's SGU2 as m2 and a float32
@@ -221,7 +221,11 @@ def load_signals_bundle(symbol, date_list, m1, m2, scaler, *, sgu1_features=None
     (gate_units.SGU2.predict_device); any other m2 / scaler gets the host
     windows as in the reference."""
     import pandas as pd
-    from .gate_units import SGU1Forest
+    from .gate_units import SGU1, SGU1Forest
+    if isinstance(m1, SGU1):
+        if m1.forest is None:
+            raise ValueError("SGU1 holds no model")
+        m1 = m1.forest
     snap_dir = os.path.join(data_root, "data", symbol, "snap")
     tick_dir = os.path.join(data_root, "data", symbol, "tick")
     days, kept = [], []

@@ -27,12 +27,21 @@ scaler fit stays on the host.
 ``SGU1Forest`` is SGU1's inference side (GateUnits.py:7-40, an
 xgboost.XGBRegressor): it reads xgboost's JSON model, packs the trees on the
 host and runs sgmm_sgu1_predict over the device feature table of
-``EventBarsGPU.sgu1_table`` (or any [n, 20] rows).  SGU1 *training* stays
-with xgboost on the host.
+``EventBarsGPU.sgu1_table`` (or any [n, 20] rows).
+
+``SGU1`` is GateUnits.py:7-40 with the fit on the device: ``train`` /
+``train_device`` / ``train_sgu1_many`` run whole fits of histogram
+gradient-boosted trees as one launch of sgmm_sgu1_train (one workgroup per
+fit, K fits per launch), ``save`` writes xgboost's JSON model.  The trainer is
+the deterministic contract of include/sgmm.h -- xgboost's objective, gain,
+weight, node numbering and early stopping over cuts that are data values --
+not xgboost's own (no quantile sketch, no subsample / colsample, no weights).
+The cuts and the exactly rounded base score are computed on the host.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -512,3 +521,352 @@ class SGU1Forest:
         tree; the analogue of Booster.predict(pred_leaf=True)'s node ids): int32 [n, n_trees]."""
         Xd, ld, n = self._matrix(X)
         return self.predict_device(Xd, ld, n, n_trees=n_trees, leaves=True)[1].cpu().numpy()
+
+
+# ----------------------------------------------------------------- SGU1 training (sgmm_sgu1_train)
+SGU1_PARAMS = {"max_depth": 4, "min_child_weight": 4, "subsample": 1.0, "colsample_bytree": 1.0,
+               "learning_rate": 0.01, "reg_alpha": 0.01, "objective": "reg:squarederror", "n_estimators": 1000,
+               "early_stopping_rounds": 20}  # GateUnits.py:12-22
+_SGU1_DEFAULTS = {"reg_lambda": 1.0, "gamma": 0.0, "max_bin": 256}  # xgboost's defaults of what the reference leaves out
+_SGU1_KNOWN = set(SGU1_PARAMS) | set(_SGU1_DEFAULTS)
+MAX_TRAIN_ROWS = 1 << 20
+_NODE_OUT = (("left", torch.int32), ("right", torch.int32), ("feature", torch.int32), ("value", torch.float32),
+             ("default_left", torch.uint8), ("base_weight", torch.float32), ("loss_change", torch.float32),
+             ("sum_hessian", torch.float32))
+
+
+def sgu1_fit_params(params) -> dict:
+    """The reference's parameter dict (xgboost's names) -> the trainer's, everything the
+    trainer does not do rejected (ValueError) before anything touches the device."""
+    p = dict(_SGU1_DEFAULTS)
+    p.update(params)
+    unknown = set(p) - _SGU1_KNOWN
+    if unknown:
+        raise ValueError(f"SGU1 parameters {sorted(unknown)} are not supported")
+    if float(p.get("subsample", 1.0)) != 1.0 or float(p.get("colsample_bytree", 1.0)) != 1.0:
+        raise ValueError("subsample / colsample_bytree other than 1 are not supported")
+    if p.get("objective", "reg:squarederror") != "reg:squarederror":
+        raise ValueError(f"objective {p['objective']!r}: only reg:squarederror is supported")
+    out = dict(max_depth=int(p["max_depth"]), min_child_weight=float(p["min_child_weight"]),
+               eta=float(p["learning_rate"]), reg_lambda=float(p["reg_lambda"]), reg_alpha=float(p["reg_alpha"]),
+               gamma=float(p["gamma"]), max_bin=int(p["max_bin"]), n_estimators=int(p["n_estimators"]),
+               early_stopping_rounds=int(p["early_stopping_rounds"] or 0))
+    if not 1 <= out["max_depth"] <= MAX_FOREST_DEPTH:
+        raise ValueError(f"max_depth {out['max_depth']} not in 1..{MAX_FOREST_DEPTH}")
+    if not 2 <= out["max_bin"] <= 256:
+        raise ValueError(f"max_bin {out['max_bin']} not in 2..256")
+    if out["n_estimators"] < 1 or out["early_stopping_rounds"] < 0:
+        raise ValueError("n_estimators < 1 or early_stopping_rounds < 0")
+    for k in ("min_child_weight", "reg_lambda", "reg_alpha", "gamma"):
+        if not (np.isfinite(out[k]) and out[k] >= 0):
+            raise ValueError(f"{k} must be finite and >= 0")
+    if not np.isfinite(out["eta"]):
+        raise ValueError("learning_rate must be finite")
+    if out["reg_lambda"] == 0 and out["min_child_weight"] == 0:
+        raise ValueError("reg_lambda and min_child_weight are both 0")
+    return out
+
+
+def sgu1_cuts(X: torch.Tensor, rows: torch.Tensor, max_bin: int):
+    """The cut rule over the training rows of the device matrix X [20, ld]: per feature the
+    sorted distinct non-NaN values v (-0 and +0 one value); v[1:] when len(v) <= max_bin,
+    else v[ceil(k len(v) / max_bin)], k = 1 .. max_bin - 1.  Not xgboost's weighted quantile
+    sketch.  Returns (cuts float32 [20, 256], n_cuts int32 [20]) on the host."""
+    cuts, n_cuts = np.zeros((len(SGU1_FEATURES), 256), np.float32), np.zeros(len(SGU1_FEATURES), np.int32)
+    Xr = X.index_select(1, rows)
+    for f in range(len(SGU1_FEATURES)):
+        col = Xr[f]
+        v = torch.unique(col[~torch.isnan(col)] + 0.0).cpu().numpy()  # sorted
+        if len(v) > max_bin:
+            k = np.arange(1, max_bin, dtype=np.int64)
+            c = v[(k * len(v) + max_bin - 1) // max_bin]
+        else:
+            c = v[1:]
+        cuts[f, :len(c)], n_cuts[f] = c, len(c)
+    return cuts, n_cuts
+
+
+def _rows(rows, ld, what):
+    rows = np.ascontiguousarray(np.asarray(rows).ravel())
+    if rows.size and (not np.issubdtype(rows.dtype, np.integer) or rows.min() < 0 or rows.max() >= ld):
+        raise ValueError(f"{what} rows outside the table of {ld} rows")
+    return rows.astype(np.int32)
+
+
+def run_sgu1_fits(specs, device="cuda"):
+    """K SGU1 fits in one launch.  specs: K dicts of X_train (float32 device matrix
+    [20, ld], sgmm_sgu1_features' layout), y_train (float32 device labels [ld]), rows_train
+    (host int rows), X_val / y_val / rows_val (or rows_val empty) and params (sgu1_fit_params'
+    output).  Returns K dicts: the node arrays of the n_trees trees back to back with
+    tree_off, base_score, val_rmse, n_trees, best_iteration (-1 without validation rows),
+    best_score, and the final float32 predictions pred_train / pred_val read from the
+    workspace (host arrays)."""
+    prepared = []
+    for k, s in enumerate(specs):  # every host-side check before the device is touched
+        p = s["params"]
+        Xt, yt = s["X_train"], s["y_train"]
+        ld_t = int(Xt.shape[1])
+        rt = _rows(s["rows_train"], ld_t, "training")
+        rv = _rows(s.get("rows_val", ()), int(s["X_val"].shape[1]) if len(s.get("rows_val", ())) else 1, "validation")
+        if not 1 <= len(rt) <= MAX_TRAIN_ROWS:
+            raise ValueError(f"fit {k}: {len(rt)} training rows, not in 1..2^20")
+        if p["early_stopping_rounds"] and not len(rv):
+            raise ValueError(f"fit {k}: early stopping needs validation rows")
+        prepared.append((rt, rv))
+    _lib.require_gpu()
+    L = _lib.load()
+    dev = torch.device(device)
+    K = len(specs)
+    tasks = (_lib.Sgu1Task * K)()
+    keep, outs, cache = [], [], {}
+    for k, s in enumerate(specs):
+        p, (rt, rv) = s["params"], prepared[k]
+        Xt, yt = s["X_train"], s["y_train"]
+        Xv, yv = (s["X_val"], s["y_val"]) if len(rv) else (None, None)
+        for t in (Xt, yt, Xv, yv):
+            if t is not None and (t.dtype != torch.float32 or t.device.type != "cuda" or not t.is_contiguous()):
+                raise TypeError("SGU1 training needs contiguous float32 tables on the device")
+        if Xt.shape[0] != len(SGU1_FEATURES) or yt.numel() < Xt.shape[1] or (
+                Xv is not None and (Xv.shape[0] != len(SGU1_FEATURES) or yv.numel() < Xv.shape[1])):
+            raise ValueError("tables are [20, ld] with ld labels")
+        key = (Xt.data_ptr(), yt.data_ptr(), rt.tobytes(), p["max_bin"])
+        if key not in cache:
+            rt_d = torch.from_numpy(rt).to(dev)
+            y_host = yt.index_select(0, rt_d.long()).cpu().numpy()
+            if not np.isfinite(y_host).all():
+                raise ValueError(f"fit {k}: non-finite training label")
+            cuts, n_cuts = sgu1_cuts(Xt, rt_d.long(), p["max_bin"])
+            base = np.float32(math.fsum(float(v) for v in y_host) / len(y_host))  # exactly rounded: no row order
+            cache[key] = (rt_d, torch.from_numpy(cuts).to(dev), torch.from_numpy(n_cuts).to(dev), base)
+        rt_d, cuts_d, ncuts_d, base = cache[key]
+        rv_d = torch.from_numpy(rv).to(dev) if len(rv) else None
+        if rv_d is not None and not bool(torch.isfinite(yv.index_select(0, rv_d.long())).all()):
+            raise ValueError(f"fit {k}: non-finite validation label")
+        n_est, stride = p["n_estimators"], (2 << p["max_depth"]) - 1
+        o = {name: torch.zeros(n_est * stride, dtype=dt, device=dev) for name, dt in _NODE_OUT}
+        o["tree_nodes"] = torch.zeros(n_est, dtype=torch.int32, device=dev)
+        o["val_rmse"] = torch.full((n_est,), float("nan"), dtype=torch.float64, device=dev)
+        o["n_trees"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        o["best_iteration"] = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        o["best_score"] = torch.full((1,), float("nan"), dtype=torch.float64, device=dev)
+        nbytes = int(L.sgmm_sgu1_train_workspace_bytes(len(rt), len(rv)))
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+        ws = ws[(-ws.data_ptr()) % 256:][:nbytes]
+        t = tasks[k]
+        t.X_train, t.y_train, t.rows_train = Xt.data_ptr(), yt.data_ptr(), rt_d.data_ptr()
+        if rv_d is not None:
+            t.X_val, t.y_val, t.rows_val = Xv.data_ptr(), yv.data_ptr(), rv_d.data_ptr()
+        t.cuts, t.n_cuts, t.workspace = cuts_d.data_ptr(), ncuts_d.data_ptr(), ws.data_ptr()
+        for name in o:
+            setattr(t, name, o[name].data_ptr())
+        t.ld_train, t.ld_val = int(Xt.shape[1]), int(Xv.shape[1]) if Xv is not None else 0
+        t.n_train, t.n_val = len(rt), len(rv)
+        t.max_depth, t.n_estimators, t.early_stopping_rounds = p["max_depth"], n_est, p["early_stopping_rounds"]
+        t.max_bin, t.base_score = p["max_bin"], float(base)
+        t.min_child_weight, t.eta, t.lambda_ = p["min_child_weight"], p["eta"], p["reg_lambda"]
+        t.alpha, t.gamma = p["reg_alpha"], p["gamma"]
+        keep += [rv_d, ws]
+        outs.append((o, ws, base, stride))
+    tasks_dev = torch.frombuffer(bytearray(bytes(tasks)), dtype=torch.uint8).to(dev)
+    check(L.sgmm_sgu1_train(ptr(tasks_dev), tasks, K, stream_ptr()), "sgmm_sgu1_train")
+    results = []
+    for k, (o, ws, base, stride) in enumerate(outs):
+        h = {name: v.cpu().numpy() for name, v in o.items()}
+        nt, counts = int(h["n_trees"][0]), h["tree_nodes"]
+        take = np.concatenate([t * stride + np.arange(counts[t]) for t in range(nt)]).astype(np.int64)
+        n_tr, n_va = tasks[k].n_train, tasks[k].n_val
+        pred = ws[:4 * (n_tr + n_va)].view(torch.float32).cpu().numpy()
+        best = int(h["best_iteration"][0])
+        results.append(dict(left=h["left"][take], right=h["right"][take], feat=h["feature"][take],
+                            value=h["value"][take], default_left=h["default_left"][take],
+                            base_weight=h["base_weight"][take], loss_change=h["loss_change"][take],
+                            sum_hessian=h["sum_hessian"][take],
+                            tree_off=np.concatenate([[0], np.cumsum(counts[:nt])]).astype(np.int64),
+                            base_score=base, val_rmse=h["val_rmse"][:nt] if n_va else np.zeros(0, np.float64),
+                            n_trees=nt, best_iteration=best, best_score=float(h["best_score"][0]),
+                            pred_train=pred[:n_tr].copy(), pred_val=pred[n_tr:].copy()))
+    return results
+
+
+def _f32_list(a):
+    return [float(str(v)) for v in np.asarray(a, np.float32)]  # the shortest decimal that reads back to the float32
+
+
+def sgu1_json(fit) -> dict:
+    """xgboost's JSON model document (Booster.save_model, version [3, 1, 3]) of a fit."""
+    nf, off, trees = len(SGU1_FEATURES), fit["tree_off"], []
+    for t in range(len(off) - 1):
+        a, b = int(off[t]), int(off[t + 1])
+        left, right = fit["left"][a:b], fit["right"][a:b]
+        parents = np.full(b - a, 2147483647, np.int64)
+        inner = np.nonzero(left != -1)[0]
+        parents[left[inner]] = parents[right[inner]] = inner
+        trees.append({
+            "base_weights": _f32_list(fit["base_weight"][a:b]), "categories": [], "categories_nodes": [],
+            "categories_segments": [], "categories_sizes": [], "default_left": fit["default_left"][a:b].tolist(),
+            "id": t, "left_children": left.tolist(), "loss_changes": _f32_list(fit["loss_change"][a:b]),
+            "parents": parents.tolist(), "right_children": right.tolist(),
+            "split_conditions": _f32_list(fit["value"][a:b]), "split_indices": fit["feat"][a:b].tolist(),
+            "split_type": [0] * (b - a), "sum_hessian": _f32_list(fit["sum_hessian"][a:b]),
+            "tree_param": {"num_deleted": "0", "num_feature": str(nf), "num_nodes": str(b - a),
+                           "size_leaf_vector": "1"}})
+    mant, exp = np.format_float_scientific(np.float32(fit["base_score"]), unique=True).split("e")
+    attributes = {"scikit_learn": '{"_estimator_type": "regressor"}'}
+    if fit["best_iteration"] >= 0:
+        attributes.update(best_iteration=str(int(fit["best_iteration"])), best_score=repr(float(fit["best_score"])))
+    return {"learner": {
+        "attributes": attributes, "feature_names": list(SGU1_FEATURES),
+        "feature_types": ["int" if n == "f_hour" else "float" for n in SGU1_FEATURES],  # the frame's dtypes
+        "gradient_booster": {"model": {
+            "cats": {"enc": [], "feature_segments": [], "sorted_idx": []},
+            "gbtree_model_param": {"num_parallel_tree": "1", "num_trees": str(len(trees))},
+            "iteration_indptr": list(range(len(trees) + 1)), "tree_info": [0] * len(trees), "trees": trees},
+            "name": "gbtree"},
+        "learner_model_param": {"base_score": f"[{mant.rstrip('.')}E{int(exp)}]", "boost_from_average": "1",
+                                "num_class": "0", "num_feature": str(nf), "num_target": "1"},
+        "objective": {"name": "reg:squarederror", "reg_loss_param": {"scale_pos_weight": "1"}}},
+        "version": [3, 1, 3]}
+
+
+def _feature_major(X):
+    """DataFrame / array [n, 20] -> float32 [20, n] (xgboost's float32 matrix, feature-major)."""
+    if hasattr(X, "columns"):
+        if tuple(X.columns) != SGU1_FEATURES:
+            raise ValueError("columns differ from SGU1DataPro.gen_dataset's")
+        X = X.to_numpy(dtype=np.float64)
+    X = np.asarray(X)
+    if X.ndim != 2 or X.shape[1] != len(SGU1_FEATURES):
+        raise ValueError(f"SGU1 rows carry {len(SGU1_FEATURES)} features")
+    return np.ascontiguousarray(X.astype(np.float32).T)
+
+
+def _host_spec(X_train, y_train, X_val, y_val, params):
+    Xt = _feature_major(X_train)
+    n_val = 0 if X_val is None else len(X_val)
+    Xv = _feature_major(X_val) if n_val else np.zeros((len(SGU1_FEATURES), 0), np.float32)
+    y = np.concatenate([np.asarray(y_train, np.float64).ravel(),
+                        np.asarray(y_val, np.float64).ravel() if n_val else np.zeros(0)]).astype(np.float32)
+    n = Xt.shape[1]
+    if len(y) != n + n_val:
+        raise ValueError("labels and rows disagree in length")
+    if not 1 <= n <= MAX_TRAIN_ROWS:
+        raise ValueError(f"{n} training rows, not in 1..2^20")
+    if params["early_stopping_rounds"] and not n_val:
+        raise ValueError("early stopping needs validation rows")
+    if not np.isfinite(y).all():
+        raise ValueError("non-finite label")
+    return dict(X=np.concatenate([Xt, Xv], axis=1), y=y, rows_train=np.arange(n), rows_val=np.arange(n, n + n_val),
+                params=params)
+
+
+def _event_rows(ev):
+    return np.concatenate([np.arange(int(a), int(a) + int(n)) for a, n in zip(ev.sgu1_row_off, ev.sgu1_n_rows)] +
+                          [np.zeros(0, np.int64)]).astype(np.int64)
+
+
+def _device_spec(ev_train, ev_val, params):
+    for ev in (ev_train, ev_val):
+        if ev is not None and not hasattr(ev, "sgu1_X"):
+            ev.sgu1_table()
+    spec = dict(X_train=ev_train.sgu1_X, y_train=(ev_train.sgu1_label * 1000).float(),  # sgu_trainer.py:48
+                rows_train=_event_rows(ev_train), params=params)
+    if ev_val is not None:
+        spec.update(X_val=ev_val.sgu1_X, y_val=(ev_val.sgu1_label * 1000).float(), rows_val=_event_rows(ev_val))
+    return spec
+
+
+class SGU1:
+    """GateUnits.py:7-40 with the fit on the device: the reference's surface (params,
+    train, predict, save, load) over sgmm_sgu1_train and an SGU1Forest.  The trainer is the
+    deterministic histogram trainer of include/sgmm.h (xgboost's objective, gain, weight,
+    node numbering and early stopping over this project's own cut rule), not xgboost's: the
+    trees differ from an xgboost fit of the same data, the file format does not.
+
+    After a fit: ``forest`` (an SGU1Forest that predicts with the first best_iteration + 1
+    trees, as XGBRegressor does after early stopping), ``evals_result``
+    ({'validation_0': {'rmse': [...]}}), ``best_iteration``, ``best_score`` and ``fit_``
+    (run_sgu1_fits' arrays)."""
+
+    def __init__(self, model_path=None, **params):
+        self.params = dict(SGU1_PARAMS)
+        self.params.update(params)
+        self.model_path = model_path
+        self.forest = self.fit_ = self._doc = None
+        self.evals_result, self.best_iteration, self.best_score = {}, None, None
+
+    def _take(self, fit):
+        self.fit_, self._doc = fit, None
+        best = fit["best_iteration"] if fit["best_iteration"] >= 0 else None
+        self.forest = SGU1Forest.from_arrays(fit["left"], fit["right"], fit["feat"], fit["value"], fit["default_left"],
+                                             fit["tree_off"], fit["base_score"], best)
+        self.evals_result = {"validation_0": {"rmse": [float(v) for v in fit["val_rmse"]]}} if best is not None else {}
+        self.best_iteration, self.best_score = best, (fit["best_score"] if best is not None else None)
+
+    def train(self, X_train, y_train, X_val=None, y_val=None):
+        """GateUnits.py:26-31: DataFrames / arrays [n, 20] and labels; one launch."""
+        train_sgu1_many([self], [(X_train, y_train, X_val, y_val)])
+
+    def train_device(self, ev_train, ev_val=None):
+        """The SGU1 branch of run_sgu_training (sgu_trainer.py:77-81) straight from the device
+        tables of two EventBarsGPU (sgu1_table's matrix, label * 1000): no host feature table."""
+        train_sgu1_many([self], [(ev_train, ev_val)])
+
+    def predict(self, X):
+        if self.forest is None:
+            raise ValueError("SGU1 holds no model")
+        return self.forest.predict(X)
+
+    def save(self, path):
+        import json
+        if self.fit_ is None and self._doc is None:
+            raise ValueError("SGU1 holds no model")
+        with open(path, "w") as fh:
+            json.dump(sgu1_json(self.fit_) if self.fit_ is not None else self._doc, fh)
+
+    def load(self, path):
+        import json
+        self.forest = SGU1Forest(path)
+        with open(path) as fh:
+            self._doc = json.load(fh)
+        attrs = self._doc["learner"].get("attributes", {})
+        self.fit_, self.evals_result = None, {}
+        self.best_iteration = self.forest.best_iteration
+        self.best_score = float(attrs["best_score"]) if "best_score" in attrs else None
+        self.model_path = path
+
+
+def train_sgu1_many(models, datasets):
+    """K independent SGU1 fits in one launch.  models: K SGU1 (each with its own params:
+    depth, learning_rate, reg_alpha, min_child_weight, ...); datasets: one dataset shared by
+    all, or K of them, each (X_train, y_train, X_val, y_val) on the host or
+    (ev_train, ev_val) -- EventBarsGPU holding their device tables.  Every model ends as
+    SGU1.train would leave it; returns the K validation histories."""
+    K = len(models)
+    if len(datasets) == 1 and K > 1:
+        datasets = list(datasets) * K
+    if len(datasets) != K:
+        raise ValueError("one dataset, or one per model")
+    params = [sgu1_fit_params(m.params) for m in models]
+    specs, uploaded = [], {}
+    for k, d in enumerate(datasets):
+        if len(d) == 2:
+            specs.append(_device_spec(d[0], d[1], params[k]))
+            continue
+        key = tuple(id(a) for a in d)
+        if key not in uploaded:
+            uploaded[key] = _host_spec(*d, params[k])
+        specs.append(dict(uploaded[key], params=params[k]))
+    for s in specs:  # host tables go up once per distinct dataset
+        if "X" in s:
+            key = id(s["X"])
+            if key not in uploaded:
+                uploaded[key] = (torch.from_numpy(s["X"]).to("cuda") if torch.cuda.is_available() else None,
+                                 torch.from_numpy(s["y"]).to("cuda") if torch.cuda.is_available() else None)
+            Xd, yd = uploaded[key]
+            if Xd is None:
+                _lib.require_gpu()
+            s.update(X_train=Xd, y_train=yd, X_val=Xd, y_val=yd)
+    fits = run_sgu1_fits(specs)
+    for m, fit in zip(models, fits):
+        m._take(fit)
+    return [m.evals_result.get("validation_0", {}).get("rmse", []) for m in models]

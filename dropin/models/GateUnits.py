@@ -4,7 +4,10 @@ checkpoint format; SGU1 stays the host xgboost regressor it is in the
 reference (GateUnits.py:7-40), built lazily so that importing this module does
 not need xgboost until an SGU1 is constructed.  SGU1Forest is its inference
 side without xgboost: it loads the JSON model SGU1.save wrote and predicts on
-the GPU (gate_units.SGU1Forest, sgmm_sgu1_predict)."""
+the GPU (gate_units.SGU1Forest, sgmm_sgu1_predict).  SGU1GPU has SGU1's
+surface with the fit on the device (gate_units.SGU1, sgmm_sgu1_train): the
+project's own deterministic histogram trainer, not xgboost's, writing the same
+JSON format."""
 import os
 import sys
 
@@ -15,6 +18,7 @@ from sgmm_amd import gate_units as _gu  # noqa: E402
 SGU2 = _gu.SGU2
 SGU2Model = _gu.SGU2Model
 SGU1Forest = _gu.SGU1Forest
+SGU1GPU = _gu.SGU1
 
 
 class SGU1:

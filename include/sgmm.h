@@ -804,6 +804,113 @@ int sgmm_sgu2_schedule(uint64_t seed, int64_t n, int32_t hidden, int32_t epochs,
                        uint8_t *keep, void *stream);
 
 /* ------------------------------------------------------------------------
+ * SGU1 training: histogram gradient-boosted trees for
+ * reg:squarederror, whole fits in one launch, one workgroup per fit.  This is
+ * a deterministic trainer of its own built from xgboost's objective, gain,
+ * weight, node-numbering and early-stopping rules; it is NOT xgboost's
+ * trainer (the cuts are not its weighted quantile sketch).  Every reduction
+ * over rows is an integer sum, so the result does not depend on thread order,
+ * the number of tasks of the launch or the order of the rows.
+ *
+ * Per round t, with pred = base_score before round 0:
+ *   g_i = pred_i - y_i (float32) over the training rows, m = max |g_i|.
+ *   m == 0: the tree is one leaf of value +0.  Otherwise, with e the binary
+ *   exponent of m (2^(e-1) <= m < 2^e), s = 40 - e and
+ *   q_i = (int64) rint((double) g_i * 2^s); the hessian is 1 per row.
+ *   A node has Q = sum q_i and H = its row count;
+ *   G = (double) Q * 2^-s; T(G) = G - alpha if G > alpha, G + alpha if
+ *   G < -alpha, else 0; gain(G, H) = T(G) * T(G) / (H + lambda).
+ *   A candidate split of a node is (feature f, cut j, missing side): rows with
+ *   x_f < cuts[f][j] go left, NaN rows go to the missing side; the missing
+ *   side is tried both ways only where the node has NaN rows of f (otherwise
+ *   right).  It is valid when H_L >= min_child_weight and
+ *   H_R >= min_child_weight; its score is (gain(L) + gain(R)) - gain(node).
+ *   The best candidate has the largest score, ties to the lowest feature, then
+ *   the lowest cut, then missing-right; the node splits iff that score is
+ *   > gamma and > 1e-6.  Growth is depth-wise up to max_depth; node ids are
+ *   xgboost's (root 0; the children of the split nodes of a level are
+ *   allocated in increasing parent id, left then right).
+ *   w = -T(G) / (H + lambda); a leaf's value is (float)(eta * w); base_weight
+ *   is (float) w at a split node and the leaf value at a leaf; loss_change is
+ *   (float) score at a split node and 0 at a leaf; sum_hessian is H.
+ *   pred_i += leaf(i) in float32 for training and validation rows (the
+ *   tree-order sum of sgmm_sgu1_predict).
+ *   Metric over the validation rows: r_i = pred_i - y_i (float32), e2 the
+ *   binary exponent of max |r_i|, s2 = 20 - e2,
+ *   SSE = sum rint((double) r_i * 2^s2)^2 (int64),
+ *   rmse = sqrt((double) SSE * 2^(-2 s2) / n_val), 0 when max |r_i| == 0:
+ *   within about 2^-20 relative of the plain RMSE, the price of a sum that
+ *   has no order.
+ *   Early stopping as xgboost's: best_iteration is the first round with a
+ *   strictly lower rmse; with early_stopping_rounds > 0 the fit ends after the
+ *   round t with t - best_iteration >= early_stopping_rounds, so it holds
+ *   best_iteration + early_stopping_rounds + 1 trees.
+ * ------------------------------------------------------------------------ */
+typedef struct sgmm_sgu1_task {
+    const float   *X_train;      /* [20, ld_train] feature-major (sgmm_sgu1_features' layout) */
+    const float   *y_train;      /* [ld_train] finite labels, indexed by row */
+    const int32_t *rows_train;   /* [n_train] rows of X_train / y_train */
+    const float   *X_val;        /* [20, ld_val]; the three may be NULL when n_val == 0 */
+    const float   *y_val;        /* [ld_val] */
+    const int32_t *rows_val;     /* [n_val] */
+    const float   *cuts;         /* [20, 256]: cuts[256 f + j], j < n_cuts[f], strictly increasing */
+    const int32_t *n_cuts;       /* [20], each 0 .. max_bin - 1 */
+    void          *workspace;    /* sgmm_sgu1_train_workspace_bytes(n_train, n_val) bytes, 256-aligned;
+                                    it begins with float pred[n_train + n_val], the running predictions
+                                    of the training rows then the validation rows, final on return */
+    /* outputs; node arrays hold n_estimators trees at a stride of 2^(max_depth + 1) - 1 nodes,
+       ids past a tree's node count are filled with -1 (children) and 0 */
+    int32_t       *left;         /* child ids, -1 at a leaf */
+    int32_t       *right;
+    int32_t       *feature;      /* 0 at a leaf */
+    float         *value;        /* the cut of a split node, the value of a leaf */
+    uint8_t       *default_left;
+    float         *base_weight;
+    float         *loss_change;
+    float         *sum_hessian;
+    int32_t       *tree_nodes;   /* [n_estimators] nodes per tree */
+    double        *val_rmse;     /* [n_estimators]; rounds >= n_trees are not written */
+    int32_t       *n_trees;      /* [1] */
+    int32_t       *best_iteration; /* [1]; -1 when n_val == 0 */
+    double        *best_score;   /* [1]; NaN when n_val == 0 */
+    int64_t        ld_train;
+    int64_t        ld_val;
+    int32_t        n_train;      /* 1 .. 2^20 */
+    int32_t        n_val;        /* >= 0 */
+    int32_t        max_depth;    /* 1 .. 6 */
+    int32_t        n_estimators; /* >= 0 */
+    int32_t        early_stopping_rounds; /* 0 = off; must be 0 when n_val == 0 */
+    int32_t        max_bin;      /* 2 .. 256 */
+    float          base_score;
+    float          reserved;
+    double         min_child_weight;
+    double         eta;
+    double         lambda;
+    double         alpha;
+    double         gamma;
+} sgmm_sgu1_task;                /* 264 bytes */
+
+/* Workspace bytes of one fit (predictions, gathered labels, the uint8 bin
+ * matrix with a missing mask per row, the row -> node map); a multiple of
+ * 256; 0 for n_train < 1 or n_val < 0. */
+size_t sgmm_sgu1_train_workspace_bytes(int64_t n_train, int64_t n_val);
+
+/* n_tasks fits in one launch (tasks: DEVICE records, tasks_host: their HOST
+ * copy for the argument checks).  A first kernel bins the rows of every task
+ * against its cuts (bin = number of cuts <= x, NaN to a missing bin) and
+ * gathers the labels; the second runs the fits.  The kernels clamp every row,
+ * bin, node and cut index they read from device memory, so malformed index
+ * lists or cuts cannot address outside their arrays; the labels must be
+ * finite and the rows inside ld (the caller checks both, they live on the
+ * device).  SGMM_ERR_ARG before any launch for: max_depth outside 1..6,
+ * max_bin outside 2..256, n_train outside 1..2^20, n_val < 0,
+ * early_stopping_rounds < 0 or > 0 with n_val == 0, negative or non-finite
+ * eta / lambda / alpha / gamma / min_child_weight, lambda == 0 with
+ * min_child_weight == 0, a NULL member. */
+int sgmm_sgu1_train(const sgmm_sgu1_task *tasks, const sgmm_sgu1_task *tasks_host, int32_t n_tasks,
+                    void *stream);
+
+/* ------------------------------------------------------------------------
  * Launch-plan overrides (ABI 5), for tests and A/B experiments.  The shipped
  * library reads no environment variable; its launch plan (policy kernel,
  * chunk groups, lane split, scan width, spill budget) follows the measured
