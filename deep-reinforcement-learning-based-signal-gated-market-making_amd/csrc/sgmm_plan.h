@@ -180,19 +180,14 @@ inline FrontierPlan frontier_plan(int32_t n, int32_t simds, const PlanKnobs& k) 
     // SGMM_PLAN_TAIL = 0 keeps every walk whole.
     const bool tail = k.tail != 0;
     const int64_t r = n % S;
-    const int fourv = k.four;
-    const bool four = fourv != 0;  // experiments: 0 = no four-walk rule, 2 = whole walks and quarters
-    if (tail && fourv == 2 && p.g0 == 1 && 4 * n - 4 * S >= 3 * (S / 2) && n < 4 * S) {
-        // experiment: four walks per SIMD as whole walks and quarters, (4n - 4S) / 3
-        // whole (config 3: 2048 whole + 512 episodes in quarters)
-        p.whole = (int32_t)((4 * n - 4 * S) / 3);
-        p.gtail = p.gmax = 4;
-    } else if (tail && four && p.g0 == 1 && 2 * n - 4 * S >= S / 2 && n < 4 * S) {
+    const bool four = k.four != 0;  // SGMM_PLAN_FOUR = 0: no four-walk rule
+    if (tail && four && p.g0 == 1 && 2 * n - 4 * S >= S / 2 && n < 4 * S) {
         // from 2.5 episodes per SIMD up to 4: four walks per SIMD, 2n - 4S whole
         // and the rest in halves, one whole and three half walks per SIMD (config
         // 3: 2560 = 1024 whole + 1536 in halves; 660.5-668.0 against 670.3-670.6 us
         // per generation for 2048 whole + 512 in halves, and 690-699 us for all in
-        // halves, profiles/r05_ab/ab20_*, ab21_*)
+        // halves, profiles/r05_ab/ab20_*, ab21_*; whole walks and quarters, 2048 +
+        // 512 in four groups, took 683-688 against 649-654 us, profiles/r06_ab/NOTES.md)
         p.whole = (int32_t)(2 * n - 4 * S);
         p.gtail = p.gmax = 2;
     } else if (tail && p.g0 == 1 && n > S && r > 0) {

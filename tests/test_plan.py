@@ -68,6 +68,10 @@ ROWS = [
     # spill: microseconds -> 10 ns units, and no fused scan with it
     ("spill50", launch(8192, spill=50), dict(spill=5000, scan="Lanes", lanes_w=2)),
     ("spill_table", launch(64, H=16, spill=50), dict(policy="TableV3", spill=0)),
+    # four is on / off: any value but 0 is the four-walk rule (1024 whole + 1536 in halves), 0
+    # leaves the tail rule (2048 whole + 512 in halves)
+    ("four2", launch(2560, four=2), dict(g0=1, gtail=2, whole=1024, gmax=2, waves=4096)),
+    ("four0", launch(2560, four=0), dict(g0=1, gtail=2, whole=2048, gmax=2, waves=3072)),
     # the walk-order feedback: whole + halves, one wave per walk, whole equal-length populations
     ("feedback", launch(2560, feedback=1, src_pop_eps=512), dict(reorder=1, w_whole=5, w_split=4)),
     ("feedback_weights", launch(2560, feedback=1, src_pop_eps=512, reorder_weights=5 << 8 | 3),
@@ -261,6 +265,10 @@ def test_boundary_tail_matrix_is_pinned():
 
 def test_groups17_is_the_default_plan(plan_rows):
     assert plan_rows["groups17"] == plan_rows["config3"]
+
+
+def test_four2_is_the_default_plan(plan_rows):
+    assert plan_rows["four2"] == plan_rows["config3"]
 
 
 @pytest.mark.parametrize("name", [r[0] for r in ONE_POP])
