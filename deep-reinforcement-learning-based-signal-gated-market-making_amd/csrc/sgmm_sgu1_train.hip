@@ -30,6 +30,7 @@ constexpr int kTrBlock = 1024;
 constexpr int kTrWaves = kTrBlock / 64;
 constexpr int kTrCutStride = 256;
 constexpr int kTrLevelNodes = 32;    // nodes of the deepest searched level (depth 6: level 5)
+constexpr int kTrMaxVal = (1 << 23) - 1;  // validation rows: n_val * (2^20)^2 < 2^63 in the metric's int64 sum
 constexpr int kBinBlock = 256;
 constexpr int kNoCand = 0x7fffffff;
 
@@ -434,8 +435,8 @@ extern "C" int sgmm_sgu1_train(const sgmm_sgu1_task* tasks, const sgmm_sgu1_task
         SGMM_REQUIRE(t.max_depth >= 1 && t.max_depth <= 6, "task %d: max_depth %d not in 1..6", k, t.max_depth);
         SGMM_REQUIRE(t.max_bin >= 2 && t.max_bin <= 256, "task %d: max_bin %d not in 2..256", k, t.max_bin);
         SGMM_REQUIRE(t.n_train >= 1 && t.n_train <= (1 << 20), "task %d: n_train %d not in 1..2^20", k, t.n_train);
-        SGMM_REQUIRE(t.n_val >= 0 && (int64_t)t.n_train + t.n_val <= INT32_MAX, "task %d: n_val %d out of range", k,
-                     t.n_val);
+        // the metric's int64 sum of n_val squares of |v| <= 2^20 stays below 2^63 up to 2^23 - 1 rows
+        SGMM_REQUIRE(t.n_val >= 0 && t.n_val <= kTrMaxVal, "task %d: n_val %d not in 0..2^23-1", k, t.n_val);
         SGMM_REQUIRE(t.n_estimators >= 0, "task %d: negative n_estimators", k);
         SGMM_REQUIRE(t.early_stopping_rounds >= 0, "task %d: negative early_stopping_rounds", k);
         SGMM_REQUIRE(t.early_stopping_rounds == 0 || t.n_val > 0,

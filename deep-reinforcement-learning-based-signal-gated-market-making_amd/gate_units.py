@@ -530,6 +530,7 @@ SGU1_PARAMS = {"max_depth": 4, "min_child_weight": 4, "subsample": 1.0, "colsamp
 _SGU1_DEFAULTS = {"reg_lambda": 1.0, "gamma": 0.0, "max_bin": 256}  # xgboost's defaults of what the reference leaves out
 _SGU1_KNOWN = set(SGU1_PARAMS) | set(_SGU1_DEFAULTS)
 MAX_TRAIN_ROWS = 1 << 20
+MAX_VAL_ROWS = (1 << 23) - 1  # the metric's int64 sum of squares of |v| <= 2^20 stays below 2^63 (include/sgmm.h)
 _NODE_OUT = (("left", torch.int32), ("right", torch.int32), ("feature", torch.int32), ("value", torch.float32),
              ("default_left", torch.uint8), ("base_weight", torch.float32), ("loss_change", torch.float32),
              ("sum_hessian", torch.float32))
@@ -606,6 +607,8 @@ def run_sgu1_fits(specs, device="cuda"):
         p = s["params"]
         Xt, yt = s["X_train"], s["y_train"]
         ld_t = int(Xt.shape[1])
+        if len(s.get("rows_val", ())) > MAX_VAL_ROWS:
+            raise ValueError(f"fit {k}: {len(s['rows_val'])} validation rows, not in 0..2^23-1")
         rt = _rows(s["rows_train"], ld_t, "training")
         rv = _rows(s.get("rows_val", ()), int(s["X_val"].shape[1]) if len(s.get("rows_val", ())) else 1, "validation")
         if not 1 <= len(rt) <= MAX_TRAIN_ROWS:
@@ -741,8 +744,10 @@ def _feature_major(X):
 
 
 def _host_spec(X_train, y_train, X_val, y_val, params):
-    Xt = _feature_major(X_train)
     n_val = 0 if X_val is None else len(X_val)
+    if n_val > MAX_VAL_ROWS:
+        raise ValueError(f"{n_val} validation rows, not in 0..2^23-1")
+    Xt = _feature_major(X_train)
     Xv = _feature_major(X_val) if n_val else np.zeros((len(SGU1_FEATURES), 0), np.float32)
     y = np.concatenate([np.asarray(y_train, np.float64).ravel(),
                         np.asarray(y_val, np.float64).ravel() if n_val else np.zeros(0)]).astype(np.float32)

@@ -876,7 +876,9 @@ typedef struct sgmm_sgu1_task {
     int64_t        ld_train;
     int64_t        ld_val;
     int32_t        n_train;      /* 1 .. 2^20 */
-    int32_t        n_val;        /* >= 0 */
+    int32_t        n_val;        /* 0 .. 2^23 - 1: the metric's SSE adds n_val squares of |v| <= 2^20
+                                    (|r| < 2^e2, so |rint(r 2^s2)| <= 2^20) in int64, and
+                                    n_val * 2^40 < 2^63 exactly when n_val <= 2^23 - 1 */
     int32_t        max_depth;    /* 1 .. 6 */
     int32_t        n_estimators; /* >= 0 */
     int32_t        early_stopping_rounds; /* 0 = off; must be 0 when n_val == 0 */
@@ -903,7 +905,8 @@ size_t sgmm_sgu1_train_workspace_bytes(int64_t n_train, int64_t n_val);
  * lists or cuts cannot address outside their arrays; the labels must be
  * finite and the rows inside ld (the caller checks both, they live on the
  * device).  SGMM_ERR_ARG before any launch for: max_depth outside 1..6,
- * max_bin outside 2..256, n_train outside 1..2^20, n_val < 0,
+ * max_bin outside 2..256, n_train outside 1..2^20, n_val outside
+ * 0..2^23-1 (beyond it the metric's int64 sum of squares could pass 2^63),
  * early_stopping_rounds < 0 or > 0 with n_val == 0, negative or non-finite
  * eta / lambda / alpha / gamma / min_child_weight, lambda == 0 with
  * min_child_weight == 0, a NULL member. */

@@ -77,7 +77,8 @@ class _Tree:
         self.left[node], self.right[node], self.feat[node], self.dl[node] = k, k + 1, int(f), int(dl)
         self.value[node] = np.float32(thr)
         self.bw[node] = np.float32(_weight(self.Q[node], self.H[node], s, P))
-        self.lc[node] = np.float32(score)
+        with np.errstate(over="ignore"):  # a score past float32 is +inf, as the device's cast
+            self.lc[node] = np.float32(score)
         for Q, H in ((QL, HL), (self.Q[node] - QL, self.H[node] - HL)):
             self.left.append(-1), self.right.append(-1), self.feat.append(0), self.dl.append(0)
             self.value.append(np.float32(0)), self.bw.append(np.float32(0)), self.lc.append(np.float32(0))

@@ -10,52 +10,35 @@ import pandas as pd
 import pytest
 
 import sgu1_model as sm
+import sgu1_train_cases as sc
 import sgu1_train_model as tm
 from conftest import has_gpu
+from sgu1_train_cases import SMALL, edge_table, model_fit, split_rows
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not has_gpu(), reason="needs a HIP device")]
 
-SMALL = dict(tm.PARAMS, n_estimators=16, early_stopping_rounds=3, eta=0.3)
 FOREST = ("left", "right", "feat", "value", "default_left", "tree_off")
 
 
-def edge_table(rng, n):
-    """Rows that take every branch of the trainer: column 1 all NaN, column 2 with NaNs that
-    belong left under x0 < 0 and right otherwise, column 3 constant, column 4 continuous
-    (more than 256 distinct values from 257 rows on), columns 5 and 6 identical, the rest a
-    small grid with a few NaNs."""
-    X = (rng.integers(-4, 5, (n, 20)) / 2).astype(np.float32)
-    X[rng.random((n, 20)) < 0.03] = np.nan
-    X[:, 0] = rng.integers(-2, 3, n)
-    X[:, 1] = np.nan
-    X[:, 2] = np.where(rng.random(n) < 0.3, np.nan, rng.integers(0, 4, n)).astype(np.float32)
-    X[:, 3] = 1.25
-    X[:, 4] = rng.normal(size=n).astype(np.float32)
-    X[:, 6] = X[:, 5]
-    x2 = X[:, 2]
-    low = X[:, 0] < 0
-    y = np.where(low, np.where(np.isnan(x2) | (x2 < 2), -2.0, 2.0), np.where(np.isnan(x2) | (x2 >= 2), 3.0, 0.0)) \
-        + np.where(X[:, 5] < 0, 1.0, 0.0) + 0.5 * X[:, 4] + 0.2 * rng.normal(size=n)
-    return X, y.astype(np.float32)
-
-
 def device_fits(cases):
-    """cases: (X [n, 20], y [n], rows_train, rows_val, params) -> run_sgu1_fits' results, one launch."""
+    """cases: (X [n, 20], y [n], rows_train, rows_val, params) or, with the validation rows in
+    a table of their own, (X, y, rows_train, rows_val, params, X_val, y_val) -> run_sgu1_fits'
+    results, one launch."""
     import torch
     from sgmm_amd import gate_units as gu
     specs, up = [], {}
-    for X, y, rt, rv, p in cases:
-        for a in (X, y):
-            if id(a) not in up:
-                up[id(a)] = torch.from_numpy(np.ascontiguousarray(a.T)).to("cuda")
-        Xd, yd = up[id(X)], up[id(y)]
-        specs.append(dict(X_train=Xd, y_train=yd, rows_train=rt, X_val=Xd, y_val=yd, rows_val=rv, params=p))
+
+    def dev(a):
+        if id(a) not in up:
+            up[id(a)] = torch.from_numpy(np.ascontiguousarray(a.T)).to("cuda")
+        return up[id(a)]
+
+    for X, y, rt, rv, p, *val in cases:
+        Xv, yv = val if val else (X, y)
+        specs.append(dict(X_train=dev(X), y_train=dev(y), rows_train=rt, X_val=dev(Xv), y_val=dev(yv), rows_val=rv,
+                          params=p))
     return gu.run_sgu1_fits(specs)
-
-
-def model_fit(X, y, rt, rv, p):
-    return tm.fit(X[rt], y[rt], X[rv] if len(rv) else None, y[rv] if len(rv) else None, **p)
 
 
 def assert_same(got, want, what=""):
@@ -64,13 +47,6 @@ def assert_same(got, want, what=""):
         assert a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes(), (what, k, a[:8], b[:8])
     assert tm.same_fit(got, want), (what, got["n_trees"], want["n_trees"], got["best_iteration"], want["best_iteration"],
                                     got["best_score"], want["best_score"])
-
-
-def split_rows(n_train, n_val):
-    """Index lists with gaps between them, as the days of a feature table leave."""
-    rt = 2 + np.arange(n_train)
-    rv = 2 + n_train + 3 + np.arange(n_val)
-    return rt, rv, 2 + n_train + 3 + n_val + 1
 
 
 @pytest.fixture(scope="module")
@@ -97,16 +73,16 @@ def test_row_counts(big, n_train):
 
 @pytest.fixture(scope="module")
 def edge(sgmm):
-    X, y = edge_table(np.random.default_rng(1), 420)
-    rt, rv, _ = split_rows(300, 110)
-    return X, y, rt, rv
+    return sc.edge()
 
 
-@pytest.mark.parametrize("depth", [1, 4, 6])
+@pytest.mark.parametrize("depth", [1, 2, 3, 4, 5, 6])
 def test_depths_and_edge_columns(edge, depth):
+    """One task per launch: the launch's largest max_depth picks k_sgu1_train<depth>."""
     X, y, rt, rv = edge
     p = dict(SMALL, max_depth=depth, min_child_weight=2.0)
-    want = model_fit(X, y, rt, rv, p)
+    assert sc.case(f"depth:{depth}")[4] == p
+    want = sc.model(f"depth:{depth}")
     got, = device_fits([(X, y, rt, rv, p)])
     assert_same(got, want, depth)
     inner = want["left"] != -1
@@ -239,6 +215,122 @@ def test_saved_model_predicts_the_trainers_predictions(edge, tmp_path):
     again = gu.SGU1()
     again.load(str(p))
     assert again.predict(X[rv]).tobytes() == pred.tobytes()
+
+
+# ---------------------------------------------------------------- the cases of tests/sgu1_train_cases.py
+#
+# What each input reaches in the model (level widths, infinite loss changes, ties, sums past
+# 2^53, ...) is asserted without a GPU in tests/test_sgu1_train_model.py; here the device
+# has to give the model's bytes on it.
+
+def check_cases(names):
+    """The named cases in one launch against the model."""
+    got = device_fits([sc.case(n) for n in names])
+    for n, g in zip(names, got):
+        assert_same(g, sc.model(n), n)
+    return got
+
+
+@pytest.mark.parametrize("depth", [6, 5])
+def test_full_levels(sgmm, depth):
+    """Depth 6: 32 nodes at level 5, one feature per pass, feature 19 in the 20th and last --
+    and every tree of both tables splits on it there.  Depth 5: 16 nodes at level 4, two
+    features per pass."""
+    check_cases([f"planted:1:{depth}", f"planted:2:{depth}"])
+
+
+def test_label_scales_in_one_launch(sgmm):
+    """2^-140 (subnormal labels, the subnormal branch of the exponent) to 2^124 (s = 40 - e
+    negative, loss_change +inf in float32); the model's fits at 2^30, 2^100 and 2^124 are
+    those of 2^0 times the power of two exactly, so the device is held to that too."""
+    got = check_cases([f"scale:{k}" for k in sc.SCALES])
+    by_k = dict(zip(sc.SCALES, got))
+    assert np.isinf(by_k[124]["loss_change"]).any() and np.isinf(by_k[100]["loss_change"]).any()
+    assert by_k[-140]["left"].tolist() == [-1] * 4 and by_k[-100]["left"].tolist() == [-1] * 4
+    assert by_k[-140]["value"].tobytes() == sc.model("scale:-140")["value"].tobytes()
+    assert by_k[124]["pred_val"].tobytes() == np.ldexp(by_k[0]["pred_val"], 124).tobytes()
+    assert by_k[124]["val_rmse"].tobytes() == np.ldexp(by_k[0]["val_rmse"], 124).tobytes()
+    assert 0 < (by_k[sc.SMALL_SCALE]["left"] != -1).sum() < (by_k[0]["left"] != -1).sum()
+
+
+def test_largest_label_scale_alone(sgmm):
+    got, = check_cases(["scale:124"])
+    assert np.isfinite(got["pred_train"]).all() and np.abs(got["pred_train"]).max() > 2.0 ** 124
+
+
+def test_subnormal_labels_that_the_metric_rounds(sgmm):
+    """2^-130: all labels subnormal and residuals of more than 20 bits, where the exponent of
+    a subnormal decides what the metric rounds to (at 2^-140 everything is exact)."""
+    got, = check_cases([f"scale:{sc.SUBNORMAL_SCALE}"])
+    assert got["n_trees"] == 4 and (got["val_rmse"] > 0).all() and (got["val_rmse"] < 2.0 ** -126).all()
+
+
+def test_rounding_ties_and_sums_past_2_53(sgmm):
+    """65 538 rows in one workgroup: rint on exact ties, a child sum of 2^54.1 that float64
+    has to round, and a leaf of the tiny rows alone whose value shows each unit of its sum."""
+    got, = check_cases(["rounding"])
+    assert got["n_trees"] == 2 and got["left"][4] == -1 and got["value"][4] != 0
+
+
+def test_infinite_and_zero_thresholds_through_save_and_predict(sgmm, tmp_path):
+    """+-inf and +-0 feature values: trained thresholds at +inf and at +0, and the saved model
+    read back into the forest kernel gives the trainer's running predictions."""
+    from sgmm_amd import gate_units as gu
+    X, y, rt, rv, p = sc.case("inf")
+    want = sc.model("inf")
+    got, = check_cases(["inf"])
+    inner = got["left"] != -1
+    assert np.isinf(got["value"][inner]).any() and not np.signbit(got["value"][inner & (got["value"] == 0)]).any()
+    m = gu.SGU1(n_estimators=16, early_stopping_rounds=3, learning_rate=0.3)
+    assert gu.sgu1_fit_params(m.params) == {k: p[k] for k in gu.sgu1_fit_params(m.params)}
+    m.train(X[rt], y[rt], X[rv], y[rv])
+    assert_same(m.fit_, want)
+    path = tmp_path / "sgu1_inf.json"
+    m.save(str(path))
+    f = gu.SGU1Forest(str(path))
+    total = len(f.tree_off) - 1
+    assert total == want["n_trees"]
+    assert np.asarray(f.value).astype(np.float32).tobytes() == want["value"].tobytes()  # inf and 0 survive the file
+    assert f.predict(X[rt], n_trees=total).tobytes() == m.fit_["pred_train"].tobytes() == want["pred_train"].tobytes()
+    assert f.predict(X[rv], n_trees=total).tobytes() == m.fit_["pred_val"].tobytes() == want["pred_val"].tobytes()
+
+
+def test_max_bins_in_one_launch(sgmm):
+    check_cases([f"max_bin:{b}" for b in sc.MAX_BINS])
+
+
+@pytest.mark.parametrize("max_bin", sc.MAX_BINS)
+def test_device_cuts_equal_the_models(sgmm, max_bin):
+    """sgu1_cuts (torch.unique on the device) against make_cuts (np.unique): the edge table,
+    +-inf and +-0 values, and columns of exactly 256 and 257 distinct values."""
+    import torch
+    from sgmm_amd import gate_units as gu
+    Xc = sc.cuts_table()
+    tables = [sc.edge()[:3:2], sc.case("inf")[:3:2], (Xc, np.arange(len(Xc))), (Xc, np.arange(len(Xc))[::-1].copy())]
+    for k, (X, rows) in enumerate(tables):
+        Xd = torch.from_numpy(np.ascontiguousarray(X.T)).to("cuda")
+        cuts, n_cuts = gu.sgu1_cuts(Xd, torch.from_numpy(rows).to("cuda"), max_bin)
+        want = tm.make_cuts(X[rows], max_bin)
+        assert cuts.dtype == np.float32 and cuts.shape == (20, 256)
+        assert n_cuts.tolist() == [len(c) for c in want], k
+        for f in range(20):
+            assert cuts[f, :n_cuts[f]].tobytes() == want[f].tobytes(), (k, f)
+            assert not cuts[f, n_cuts[f]:].any()
+    if max_bin == 256:
+        want = tm.make_cuts(Xc, 256)
+        assert want[0].tolist() == list(range(1, 256)) and want[1].tolist() == list(range(2, 257))
+
+
+def test_rows_and_tables_in_one_launch(sgmm):
+    """Validation rows from a second table with its own leading dimension, one validation
+    row, a bootstrap sample of the training rows (repeated indices), min_child_weight 2.5
+    and 0."""
+    got = dict(zip(sc.ROWS_AND_TABLES, check_cases(list(sc.ROWS_AND_TABLES))))
+    assert len(got["one_val_row"]["pred_val"]) == 1 and len(got["one_val_row"]["val_rmse"]) == 16
+    assert len(got["second_table"]["pred_val"]) == len(sc.case("second_table")[3])
+    kids = np.ones(len(got["mcw0"]["left"]), bool)
+    kids[got["mcw0"]["tree_off"][:-1]] = False
+    assert got["mcw0"]["sum_hessian"][kids].min() == 1.0 and got["mcw2.5"]["sum_hessian"].min() == 3.0
 
 
 # ---------------------------------------------------------------- the g14 fixture, end to end

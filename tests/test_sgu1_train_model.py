@@ -28,6 +28,7 @@ import numpy as np
 import pytest
 
 import sgu1_model as sm
+import sgu1_train_cases as sc
 import sgu1_train_model as tm
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
@@ -286,6 +287,232 @@ def test_sanity_on_a_planted_tree():
     assert abs(r["val_rmse"][-1] - plain) <= 2.0 ** -18 * plain
 
 
+# ---------------------------------------------------------------- the cases of the GPU tests reach their edges
+#
+# tests/test_gpu_sgu1_train.py compares the device with the model on the inputs of
+# tests/sgu1_train_cases.py.  That says something only where the model, on that input,
+# really takes the path the case is built for: asserted here, from the model alone.
+
+def splits(r):
+    return r["left"] != -1
+
+
+def children(r):
+    """Every node but the roots."""
+    c = np.ones(len(r["left"]), bool)
+    c[r["tree_off"][:-1]] = False
+    return c
+
+
+@pytest.mark.parametrize("depth", [1, 2, 3, 4, 5, 6])
+def test_case_depths_reach_their_last_level(depth):
+    """A: at every max_depth some tree has a node at that depth, so a launch of that depth
+    alone needs the node tables of its own k_sgu1_train<D>."""
+    r = sc.model(f"depth:{depth}")
+    sizes = np.diff(r["tree_off"])
+    deepest = max(len(sc.level_widths(r, t)[0]) - 1 for t in range(r["n_trees"]))
+    print(f"depth {depth}: largest tree {sizes.max()} nodes, deepest level {deepest}")
+    assert deepest == depth and 2 ** depth - 1 < sizes.max() <= 2 ** (depth + 1) - 1
+    if depth > 1:
+        assert not tm.same_fit(r, sc.model(f"depth:{depth - 1}"))
+
+
+@pytest.mark.parametrize("variant", [1, 2])
+def test_case_planted_levels_are_full(variant):
+    """B: every tree has 32 nodes at depth 5 (the level searched one feature per pass, 20
+    passes) and splits there on feature 19, the feature of the last pass; at max_depth 5 the
+    last searched level has 16 nodes (two features per pass)."""
+    r = sc.model(f"planted:{variant}:6")
+    assert r["n_trees"] == 4
+    for t in range(4):
+        w, depth = sc.level_widths(r, t)
+        a, b = r["tree_off"][t], r["tree_off"][t + 1]
+        at5 = splits(r)[a:b] & (depth == 5)
+        print(f"variant {variant} tree {t}: widths {w.tolist()}, features split at depth 5 "
+              f"{sorted(set(r['feat'][a:b][at5].tolist()))}")
+        assert w[:6].tolist() == [1, 2, 4, 8, 16, 32] and len(w) == 7
+        assert 19 in r["feat"][a:b][at5]
+        if variant == 1:
+            assert w[6] == 64  # 127 nodes: every node of every level splits
+    X, y, rt, _, _ = sc.case(f"planted:{variant}:6")
+    assert set(np.unique(X[rt][:, sc.PLANTED_COLS]).tolist()) == {-1.0, 1.0}
+    r5 = sc.model(f"planted:{variant}:5")
+    for t in range(4):
+        assert sc.level_widths(r5, t)[0].tolist() == [1, 2, 4, 8, 16, 32]
+
+
+def test_case_planted_equals_bruteforce():
+    X, y, rt, rv, p = sc.case("planted:1:6")
+    assert all(len(np.unique(X[rt, f][~np.isnan(X[rt, f])])) <= 256 for f in range(20))
+    b = sc.model_fit(X, y, rt, rv, p, fit=tm.fit_bruteforce)
+    a = sc.model("planted:1:6")
+    assert tm.same_fit(a, b) and a["pred_train"].tobytes() == b["pred_train"].tobytes()
+
+
+@pytest.mark.parametrize("k", [30, 100, 124])
+def test_case_scales_up_are_exact(k):
+    """C: a power of two on the labels moves nothing but the scale -- the same trees, every
+    leaf, prediction and rmse times 2^k exactly.  That pins the model without itself."""
+    r0, r = sc.model("scale:0"), sc.model(f"scale:{k}")
+    y0, y = sc.case("scale:0")[1], sc.case(f"scale:{k}")[1]
+    assert y.dtype == np.float32 and np.isfinite(y).all()
+    assert (y.astype(np.float64) == np.ldexp(y0.astype(np.float64), k)).all()
+    for name in ("left", "right", "feat", "default_left", "tree_off"):
+        assert r[name].tobytes() == r0[name].tobytes(), name
+    leaf = ~splits(r0)
+    assert r["value"][~leaf].tobytes() == r0["value"][~leaf].tobytes()  # thresholds: the features did not move
+    assert r["value"][leaf].tobytes() == np.ldexp(r0["value"][leaf], k).tobytes()
+    assert r["pred_train"].tobytes() == np.ldexp(r0["pred_train"], k).tobytes()
+    assert r["pred_val"].tobytes() == np.ldexp(r0["pred_val"], k).tobytes()
+    assert r["val_rmse"].tobytes() == np.ldexp(r0["val_rmse"], k).tobytes()
+    assert (r["n_trees"], r["best_iteration"]) == (r0["n_trees"], r0["best_iteration"])
+    n_inf = int(np.isinf(r["loss_change"]).sum())
+    print(f"k {k}: {len(r['left'])} nodes, {r['n_trees']} trees, {n_inf} infinite loss_change")
+    assert len(r["left"]) > 400 and r["n_trees"] == 16
+    if k >= 100:
+        assert n_inf > 0 and (r["loss_change"][np.isinf(r["loss_change"])] > 0).all()
+    else:
+        assert n_inf == 0
+
+
+def test_case_scales_down_meet_the_absolute_rule():
+    """C: the split rule score > 1e-6 is absolute.  Scores go with 2^2k: at 2^-6 every split
+    of k = 0 still clears it on this table, 2^-7 is the nearest scale that loses some; at
+    2^-100 and below nothing splits and the fit ends by early stopping; at 2^-140 the
+    labels are subnormal."""
+    n0 = int(splits(sc.model("scale:0")).sum())
+    X, y, rt, rv, p = sc.case("scale:0")
+    n6 = int(splits(sc.model_fit(X, np.ldexp(y, -6), rt, rv, p)).sum())
+    n7 = int(splits(sc.model(f"scale:{sc.SMALL_SCALE}")).sum())
+    print(f"split nodes: k 0 {n0}, k -6 {n6}, k {sc.SMALL_SCALE} {n7}")
+    assert sc.SMALL_SCALE == -7 and n6 == n0 and 1 <= n7 < n0
+    for k in (-100, -140):
+        r = sc.model(f"scale:{k}")
+        assert r["n_trees"] == r["best_iteration"] + 3 + 1 < 16 and len(r["left"]) == r["n_trees"]
+        print(f"k {k}: {r['n_trees']} single-leaf trees")
+    y = sc.case("scale:-140")[1][rt]
+    assert ((y != 0) & (np.abs(y) < np.finfo(np.float32).tiny)).any()
+    assert sc.SCALES == (-140, -100, -7, 0, 30, 100, 124)
+
+
+def test_case_subnormal_scale_shows_the_exponent(monkeypatch):
+    """C: at 2^-130 every label is subnormal and the metric has to round (a residual times
+    2^s2 is no integer), so the exponent of a subnormal matters: the model with that exponent
+    off by one, either way, gives another rmse.  At 2^-140 it gives the same bytes -- all
+    quantisations are exact there -- which is why that scale alone would not pin it."""
+    k = sc.SUBNORMAL_SCALE
+    X, y, rt, rv, p = sc.case(f"scale:{k}")
+    tiny = np.finfo(np.float32).tiny
+    assert ((y[rt] != 0) & (np.abs(y[rt]) < tiny)).all() and ((y[rv] != 0) & (np.abs(y[rv]) < tiny)).all()
+    want = sc.model(f"scale:{k}")
+    r = (want["pred_val"] - y[rv]).astype(np.float64)
+    e2 = tm._exponent(np.abs(r).max())
+    scaled = np.ldexp(r, 20 - e2)
+    print(f"k {k}: exponent of the largest residual {e2}, {int((scaled != np.rint(scaled)).sum())} of {len(r)} round")
+    assert e2 <= -126 and (scaled != np.rint(scaled)).any()
+    real, want140 = tm._exponent, sc.model("scale:-140")  # the shared fits are computed before the patch
+    for delta in (1, -1):
+        monkeypatch.setattr(tm, "_exponent", lambda m, d=delta: real(m) + (d if np.float32(m) < tiny else 0))
+        assert sc.model_fit(X, y, rt, rv, p)["val_rmse"].tobytes() != want["val_rmse"].tobytes()
+        assert tm.same_fit(sc.model_fit(*sc.case("scale:-140")), want140)
+
+
+def away(x):
+    """Round half away from zero: what round() does where rint goes to even."""
+    return (np.sign(x) * np.floor(np.abs(x) + 0.5)).astype(np.int64)
+
+
+def test_case_rounding_rounds_ties_and_passes_2_53():
+    """D: base_score exactly 0; round-0 gradients that are exact ties; the left child of the
+    root sums to more than 2^53 and float64 cannot hold the sum (here it lies halfway
+    between two float64, a tie of its own).  And the properties that let a wrong rounding
+    show: the tiny rows under that child end in a leaf of their own, whose sum differs
+    between rint and round, is no multiple of 4, and stands in the leaf's value."""
+    X, y, rt, rv, p = sc.case("rounding")
+    r = sc.model("rounding")
+    assert len(y) == 65538 and len(rt) == 65538 and len(rv) == 64
+    assert tm.base_score(y) == 0.0 and not np.signbit(tm.base_score(y))
+    g = np.float32(0.0) - y
+    s = 40 - tm._exponent(np.abs(g).max())
+    x = np.ldexp(g.astype(np.float64), s)
+    q = np.rint(x).astype(np.int64)
+    ties = np.abs(x) % 1 == 0.5
+    assert s == 39 and ties.sum() == 2 * sc.N_TIE and (q[ties] != away(x[ties])).any()
+    assert r["feat"][0] == 0 and r["value"][0] == 1.0 and r["left"][0] == 1
+    L = X[:, 0] < r["value"][0]
+    Q = int(q[L].sum())
+    print(f"{int(ties.sum())} ties; |Q_L| = 2^{np.log2(abs(Q)):.2f}, Q_L mod 4 = {Q % 4}")
+    assert abs(Q) >= 2 ** 53 and int(float(Q)) != Q
+    assert 2 ** 54 <= abs(Q) < 2 ** 55 and Q % 4 == 2  # float64 steps by 4 here: halfway
+    # node 1 (the left child) splits the tiny rows off: node 4 is their leaf
+    tiny = L & (X[:, 1] == 3.0)
+    assert (r["feat"][1], r["value"][1], r["left"][1], r["right"][1]) == (1, 3.0, 3, 4) and r["left"][4] == -1
+    assert r["sum_hessian"][4] == tiny.sum() and (np.abs(y[tiny]) < 2.0 ** -33).all()
+    Qt, Qt_away = int(q[tiny].sum()), int(away(x[tiny]).sum())
+    print(f"tiny leaf: {int(tiny.sum())} rows, Q = {Qt} (rint), {Qt_away} (half away from zero)")
+    assert Qt != Qt_away and Qt % 4 != 0
+    want = np.float32(p["eta"] * -(np.ldexp(float(Qt), -s) / (float(tiny.sum()) + p["reg_lambda"])))
+    assert r["value"][4].tobytes() == want.tobytes()
+    assert want != np.float32(p["eta"] * -(np.ldexp(float(Qt_away), -s) / (float(tiny.sum()) + p["reg_lambda"])))
+    assert want != np.float32(p["eta"] * -(np.ldexp(float(Qt & ~3), -s) / (float(tiny.sum()) + p["reg_lambda"])))
+    assert r["n_trees"] == 2 and np.diff(r["tree_off"]).tolist() == [7, 7]
+
+
+def test_case_inf_and_signed_zero_thresholds():
+    """E: trained thresholds at +inf and at 0, the 0 never negative, and the brute-force
+    model agrees (every column has at most 256 distinct values on the training rows)."""
+    X, y, rt, rv, p = sc.case("inf")
+    r = sc.model("inf")
+    x4, x5 = X[rt, 4], X[rt, 5]
+    assert (x4 == np.inf).sum() > 10 and (x4 == -np.inf).sum() > 10
+    assert ((x5 == 0) & np.signbit(x5)).any() and ((x5 == 0) & ~np.signbit(x5)).any()
+    inner = splits(r)
+    zero = inner & (r["value"] == 0)
+    n_inf, n_zero5 = int(np.isinf(r["value"][inner]).sum()), int((zero & (r["feat"] == 5)).sum())
+    print(f"{n_inf} infinite thresholds, {n_zero5} zero thresholds on feature 5")
+    assert n_inf > 0 and (r["feat"][inner & np.isinf(r["value"])] == 4).all()
+    assert n_zero5 > 0 and not np.signbit(r["value"][zero]).any()
+    assert all(len(np.unique(X[rt, f][~np.isnan(X[rt, f])])) <= 256 for f in range(20))
+    b = sc.model_fit(X, y, rt, rv, p, fit=tm.fit_bruteforce)
+    assert tm.same_fit(r, b) and r["pred_val"].tobytes() == b["pred_val"].tobytes()
+
+
+def test_case_max_bin_cut_counts():
+    X, _, rt, _ = sc.edge()
+    assert len(np.unique(X[rt, 4])) > 256
+    counts = [len(sc.model(f"max_bin:{b}")["cuts"][4]) for b in sc.MAX_BINS]
+    print(f"cuts of column 4 at max_bin {sc.MAX_BINS}: {counts}")
+    assert counts == [1, 2, 254, 255]
+    for b in sc.MAX_BINS:
+        r = sc.model(f"max_bin:{b}")
+        assert (splits(r) & (r["feat"] == 4)).any()
+        assert all(len(c) <= b - 1 for c in r["cuts"])
+    assert len({sc.model(f"max_bin:{b}")["value"].tobytes() for b in sc.MAX_BINS}) == 4
+    cuts = tm.make_cuts(sc.cuts_table(), 256)
+    assert len(cuts[0]) == 255 and len(cuts[1]) == 255 and cuts[0][0] == 1 and cuts[1][0] == 2
+
+
+def test_case_rows_and_tables():
+    """F: what each case of the rows-and-tables launch is there for."""
+    X, y, rt, rv = sc.edge()
+    c = sc.case("second_table")
+    assert len(c) == 7 and len(c[5]) != len(X) and c[3].max() < len(c[5]) and len(set(c[3].tolist())) < len(c[3])
+    assert len(sc.model("second_table")["val_rmse"]) == 16
+    assert len(sc.case("one_val_row")[3]) == 1 and len(sc.model("one_val_row")["pred_val"]) == 1
+    rb = sc.case("bootstrap")[2]
+    assert len(rb) == 300 and len(set(rb.tolist())) < 250 and set(rb.tolist()) <= set(rt.tolist())
+    assert not tm.same_fit(sc.model("bootstrap"), sc.model("depth:4"))
+    # 2.5 admits what 3 admits and not what 2 admits: the comparison is in float64, not truncated
+    r = sc.model("mcw2.5")
+    assert r["sum_hessian"][children(r)].min() == 3.0
+    assert tm.same_fit(r, sc.model_fit(X, y, rt, rv, dict(sc.SMALL, min_child_weight=3.0)))
+    assert not tm.same_fit(r, sc.model("depth:4")) and sc.case("depth:4")[4]["min_child_weight"] == 2.0
+    # min_child_weight 0 admits empty children; they score 0 and never win
+    r = sc.model("mcw0")
+    print(f"min_child_weight 0: {len(r['left'])} nodes, smallest child {r['sum_hessian'][children(r)].min()}")
+    assert r["sum_hessian"][children(r)].min() == 1.0 and len(r["left"]) > 1000
+
+
 # ---------------------------------------------------------------- argument checks, no GPU
 
 def host_task(_lib, **over):
@@ -304,6 +531,8 @@ def host_task(_lib, **over):
     (dict(lambda_=0.0, min_child_weight=0.0), b"both 0"), (dict(X_train=None), b"null training"),
     (dict(rows_val=None), b"null validation"), (dict(cuts=None), b"null cuts"), (dict(workspace=None), b"workspace"),
     (dict(workspace=260), b"workspace"), (dict(val_rmse=None), b"null output"), (dict(n_estimators=-1), b"n_estimators"),
+    # the metric's int64 sum is safe up to 2^23 - 1 validation rows: 2^23 is refused, 2^23 - 1 gets past that check
+    (dict(n_val=1 << 23), b"n_val"), (dict(n_val=(1 << 23) - 1, workspace=None), b"workspace"),
 ])
 def test_c_abi_rejects_before_any_launch(sgmm, over, msg):
     from sgmm_amd import _lib
@@ -356,6 +585,16 @@ def test_sgu1_rejects_bad_data(sgmm):
         gu.run_sgu1_fits([dict(X_train=np.zeros((20, 10), np.float32), y_train=np.zeros(10, np.float32),
                                rows_train=np.array([0, 10]), params=gu.sgu1_fit_params(dict(gu.SGU1_PARAMS,
                                                                                              early_stopping_rounds=0)))])
+    # 2^23 validation rows: the metric's int64 sum of squares could pass 2^63 (include/sgmm.h, n_val)
+    many = 1 << 23
+    assert gu.MAX_VAL_ROWS == many - 1 and (many - 1) << 40 < 1 << 63 <= many << 40
+    with pytest.raises(ValueError, match=r"2\^23"):
+        m.train(X, y, np.broadcast_to(np.float32(0), (many, 20)), np.broadcast_to(np.float64(0), (many,)))
+    with pytest.raises(ValueError, match=r"2\^23"):
+        gu.run_sgu1_fits([dict(X_train=np.zeros((20, 10), np.float32), y_train=np.zeros(10, np.float32),
+                               rows_train=np.arange(10), X_val=np.zeros((20, 10), np.float32),
+                               y_val=np.zeros(10, np.float32), rows_val=np.broadcast_to(np.int64(0), (many,)),
+                               params=gu.sgu1_fit_params(gu.SGU1_PARAMS))])
     with pytest.raises(ValueError):
         m.predict(X)
 
