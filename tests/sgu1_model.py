@@ -60,12 +60,21 @@ def forest_predict(left, right, feat, value, default_left, tree_off, base_score,
     return pred, leaf
 
 
-def roll_mean(v, w):
+def roll_mean(v, w, stats=None):
     """Series(v).rolling(w, min_periods=1).mean() for NaN-free v, bit for bit: pandas keeps
     one running sum per series with separate Kahan compensations for the values it adds and
-    the values it removes; a window of one is set up afresh at every index."""
+    the values it removes; a window of one is set up afresh at every index.
+
+    ``stats``: a dict that receives, per index, which override of calc_mean decided the value
+    and changed its bits -- ``same`` (all values of the window equal, and sum / nobs is another
+    number or a zero of the other sign), ``clamp_nonneg`` (no negative value, a negative mean)
+    and ``clamp_neg`` (all negative, a positive mean) -- and ``neg``, the window's count of
+    values with the sign bit set."""
     v = np.asarray(v, np.float64)
     out = np.empty(len(v))
+    if stats is not None:
+        stats.update(same=np.zeros(len(v), bool), clamp_nonneg=np.zeros(len(v), bool),
+                     clamp_neg=np.zeros(len(v), bool), neg=np.zeros(len(v), np.int64))
     s = c_add = c_rm = 0.0
     nobs = neg = same = 0
     prev = v[0] if len(v) else 0.0
@@ -92,6 +101,12 @@ def roll_mean(v, w):
         same = same + 1 if x == prev else 1
         prev = x
         r = s / nobs
+        if stats is not None:
+            stats["neg"][i] = neg
+            if same >= nobs:
+                stats["same"][i] = r != prev or np.signbit(r) != np.signbit(prev)
+            else:
+                stats["clamp_nonneg"][i], stats["clamp_neg"][i] = neg == 0 and r < 0, neg == nobs and r > 0
         if same >= nobs:
             r = prev
         elif neg == 0 and r < 0:
@@ -147,10 +162,14 @@ def bar_mids(ev):
     return (np.asarray(ev["askprice1"], np.float64)[last] + np.asarray(ev["bidprice1"], np.float64)[last]) / 2.0
 
 
-def feature_table(ev):
+def feature_table(ev, stats=None):
     """SGU1DataPro.gen_dataset(19) of one day's event bars by the rules of DESIGN §9 row f6
     (numpy's pairwise sums from oracle/bundle_oracle.py, roll_mean and slope_closed above):
-    float64 [rows, 21], the 20 features then label; no row below 6 bars."""
+    float64 [rows, 21], the 20 features then label; no row below 6 bars.
+
+    ``stats``: a dict that receives the per-bar intermediates -- ``branch`` (1 .. 4, the arm of
+    the label's NaN fallback), ``x`` (the label before rounding), ``vwap``, ``hour`` and
+    ``roll`` ({window: the stats of roll_mean})."""
     import bundle_oracle as bo
     col = {c: np.asarray(ev[c], np.int64 if c == "trade_time" else np.float64) for c in EV_COLS}
     starts = list(range(0, len(col["trade_time"]) - 19, 19))
@@ -158,19 +177,20 @@ def feature_table(ev):
     if nb < 6:
         return np.zeros((0, 21))
     nansum = lambda a: bo.pairwise_sum(np.where(np.isnan(a), 0.0, a))
-    tr, vwap, mid, lab, spread, imb, vol, hour = (np.empty(nb) for _ in range(8))
+    tr, vwap, mid, lab, spread, imb, vol, hour, xs, branch = (np.empty(nb) for _ in range(10))
     for b, a in enumerate(starts):
         g = {c: v[a:a + 19] for c, v in col.items()}
         bmax, smin = bo.nanmax(g["p_buy_max"]), bo.nanmin(g["p_sell_min"])
         am, bm = bo.skipna_mean(g["askprice1"]), bo.skipna_mean(g["bidprice1"])
         if not np.isnan(bmax) and not np.isnan(smin):
-            x = bmax - smin
+            x, branch[b] = bmax - smin, 1
         elif not np.isnan(smin):
-            x = am - smin
+            x, branch[b] = am - smin, 2
         elif not np.isnan(bmax):
-            x = bmax - bm
+            x, branch[b] = bmax - bm, 3
         else:
-            x = am - bm
+            x, branch[b] = am - bm, 4
+        xs[b] = x
         lab[b] = np.rint(np.float64(x) * 1e4) / 1e4
         v = nansum(g["vol_sum"])
         tr[b], vol[b] = nansum(g["trade_count"]), v
@@ -183,12 +203,15 @@ def feature_table(ev):
     out = np.empty((nb, 21))
     for j, w in enumerate((1, 2, 3, 5, 10)):
         out[:, j] = [tr[max(q - w + 1, 0):q + 1].sum() for q in p]
+    roll = {w: {} for w in (1, 3, 5)}
     for j, w in enumerate((1, 3, 5)):
-        out[:, 5 + j] = roll_mean(vwap, w)[p]
+        out[:, 5 + j] = roll_mean(vwap, w, roll[w] if stats is not None else None)[p]
         out[:, 8 + j] = [slope_closed(y) for y in window_slopes(mid, w)]
     for L in range(1, 6):
         out[:, 10 + L] = lab[np.maximum(np.arange(nb) - L, 0)]
     out[:, 16], out[:, 17], out[:, 18], out[:, 19], out[:, 20] = spread[p], imb[p], vol[p], hour, lab
+    if stats is not None:
+        stats.update(branch=branch.astype(np.int64), x=xs, vwap=vwap, hour=hour.astype(np.int64), roll=roll)
     return out
 
 

@@ -15,7 +15,18 @@ reference worst 1.54 * 2^-52 * max|mid|.  Where the exact slope vanishes (a flat
 or a symmetric window) the kernel gives exactly +0.0 (or the last-bit noise
 of the mids) and polyfit +-1e-16: the one place the float32 matrices differ
 (30 slope entries of the fixture), asserted to be confined to slopes below
-one ulp of the mids."""
+one ulp of the mids.
+
+The fixture days leave most value-dependent branches of the feature kernel
+untaken; the generated edge days of tests/sgu1_feature_cases.py (which
+tests/test_sgu1_model.py holds to pandas on the CPU) carry them through it and
+are compared with the model byte for byte, the sign of a zero included.
+Kernel variants run once on an MI355X against these tests: without the "all
+equal" override of the rolling mean the rolling, ties, hours, turns and full
+days fail, without the two clamps the rolling, turns and full days, with
+floor(x * 1e4 + 0.5) for rint the ties, turns and full days, and with float32
+denormals flushed the cast day; none of the first three failed a test of the
+fixture days."""
 import ctypes
 from fractions import Fraction
 
@@ -23,6 +34,7 @@ import numpy as np
 import pandas as pd
 import pytest
 
+import sgu1_feature_cases as fc
 import sgu1_model as sm
 from conftest import has_gpu
 
@@ -37,6 +49,18 @@ SLOPES = (9, 10)
 def same(a, b):
     a, b = np.asarray(a), np.asarray(b)
     return a.shape == b.shape and np.array_equal(a.astype(np.float64), b.astype(np.float64), equal_nan=True)
+
+
+def same_bytes(a, b):
+    """Equal shape, type and bytes: array_equal would hide the sign of a zero."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def cast32(F):
+    """numpy's float64 -> float32 cast (to nearest even; inf past FLT_MAX + half an ulp)."""
+    with np.errstate(over="ignore", under="ignore"):
+        return np.asarray(F, np.float64).astype(np.float32)
 
 
 @pytest.fixture(scope="module")
@@ -139,15 +163,80 @@ def test_one_launch_equals_day_by_day(g14, table):
         assert np.array_equal(one.sgu1_F64[:, a:a + n].cpu().numpy().T, days[k][0]), k
 
 
-def test_sentinels_behind_every_output(sgmm, g14):
-    """Rows outside row_off[d] .. +n_rows[d] stay untouched in X, F64 and label, for every
-    feature; without F64 the float32 matrix is the same."""
+# ---------------------------------------------------------------- the edge days (sgu1_feature_cases.py)
+
+def launch(bars):
+    """One launch: (EventBarsGPU, per day (F64 [rows, 20], X [rows, 20], label [rows]))."""
+    from sgmm_amd.bundle import EventBarsGPU
+    ev = EventBarsGPU.from_bars(bars)
+    days = []
+    for d, (X, label) in enumerate(ev.sgu1_table()):
+        a, n = int(ev.sgu1_row_off[d]), int(ev.sgu1_n_rows[d])
+        days.append((ev.sgu1_F64[:, a:a + n].cpu().numpy().T, X.cpu().numpy().T, label.cpu().numpy()))
+    return ev, days
+
+
+def assert_day_is_the_models(got, want, tag):
+    """The float64 table, the label and the float32 matrix, byte for byte, column by column."""
+    F64, X, label = got
+    assert F64.shape == (len(want), 20) and X.shape == (len(want), 20) and label.shape == (len(want),), tag
+    assert F64.dtype == np.float64 and X.dtype == np.float32 and label.dtype == np.float64
+    want32 = cast32(want[:, :20])
+    for j in range(20):
+        bad = np.nonzero(F64[:, j].view(np.uint64) != want[:, j].view(np.uint64))[0]
+        assert not len(bad), (tag, sm.FEATURES[j], len(bad), bad[:5], F64[bad[:5], j], want[bad[:5], j])
+        bad = np.nonzero(X[:, j].view(np.uint32) != want32[:, j].view(np.uint32))[0]
+        assert not len(bad), (tag, sm.FEATURES[j], "float32", len(bad), bad[:5], X[bad[:5], j], want32[bad[:5], j])
+    assert same_bytes(label, want[:, 20]), tag
+    assert same_bytes(F64, want[:, :20]) and same_bytes(X, want32), tag
+
+
+@pytest.mark.parametrize("name", ["rolling", "ties", "cast", "hours"])
+def test_edge_day_is_the_models(sgmm, name):
+    """Each edge day through the kernel: calc_mean's three overrides and the signbit count
+    (rolling), rint on exact ties (ties), the float32 cast at overflow, subnormals, underflow
+    and halfway cases (cast), the integer division of trade_time (hours)."""
+    want, _ = fc.table(name)
+    ev, days = launch([fc.day(name)])
+    assert ev.sgu1_n_rows.tolist() == [len(want)]
+    assert_day_is_the_models(days[0], want, name)
+    if name == "rolling":  # the closed-form slopes against the exact least-squares slope
+        mid = sm.bar_mids(fc.day(name))
+        for s, j in ((3, 9), (5, 10)):
+            for r, y in enumerate(sm.window_slopes(mid, s)):
+                bound = 4 * 2.0 ** -52 * float(np.abs(y).max())
+                assert abs(float(Fraction(float(days[0][0][r, j])) - sm.slope_exact(y))) <= bound, (j, r)
+    if name == "hours":
+        df = ev.sgu1_frame(0)
+        assert df["f_hour"].dtype == np.int64
+        assert df["f_hour"].tolist() == [t // 10 ** 7 for t in fc.HOURS]
+
+
+def test_turns_in_one_launch_and_alone(sgmm):
+    """6, 7, 1023, 1024, 1025, 2048 and 2049 bars in one launch, a 5-bar and an empty day
+    between them: every day is the model's, and a day launched alone has the same bytes."""
+    bars = fc.turns()
+    ev, days = launch(bars)
+    assert ev.sgu1_n_rows.tolist() == [nb if nb >= 6 else 0 for nb in fc.TURNS]
+    for k, nb in enumerate(fc.TURNS):
+        if nb < 6:
+            assert days[k][0].shape == (0, 20) and days[k][2].shape == (0,)
+            continue
+        assert_day_is_the_models(days[k], fc.table(str(k))[0], nb)
+        _, alone = launch([bars[k]])
+        assert all(same_bytes(a, b) for a, b in zip(alone[0], days[k])), nb
+
+
+def sentinel_launch(bars, want, whole=()):
+    """One launch with gaps between the days and behind the last: rows outside
+    row_off[d] .. +n_rows[d] stay untouched in X, F64 and label, for every feature; without F64
+    the float32 matrix has the same bytes.  want: per day the table [rows, 21]; the days listed
+    in ``whole`` are held to it on every column, byte for byte."""
     import torch
     from sgmm_amd._lib import check, ptr, stream_ptr
     from sgmm_amd.bundle import EventBarsGPU
-    bars = fixture_bars(g14)
     ev = EventBarsGPU.from_bars(bars)
-    n = [len(g14[f"d{k}_table"]) for k in range(len(bars))]
+    n = [len(w) for w in want]
     gap = 3
     row_off = np.concatenate([[gap], gap + np.cumsum([v + gap for v in n])]).astype(np.int64)
     ld = int(row_off[-1]) + 5
@@ -166,16 +255,37 @@ def test_sentinels_behind_every_output(sgmm, g14):
         assert nr.tolist() == n + [-77, -77]
         inside = np.zeros(ld, bool)
         for d in range(len(bars)):
-            inside[row_off[d]:row_off[d] + n[d]] = True
-            want = g14[f"d{d}_table"]
+            rows = slice(row_off[d], row_off[d] + n[d])
+            inside[rows] = True
             if n[d]:
-                assert np.array_equal(lab[row_off[d]:row_off[d] + n[d]], want[:, 20])
-                assert np.array_equal(X[0, row_off[d]:row_off[d] + n[d]], want[:, 0].astype(np.float32))
+                assert np.array_equal(lab[rows], want[d][:, 20])
+                assert np.array_equal(X[0, rows], want[d][:, 0].astype(np.float32))
+            if d in whole:
+                assert same_bytes(lab[rows], want[d][:, 20]), d
+                assert same_bytes(X[:, rows].T, cast32(want[d][:, :20])), (d, with_f64)
+                assert not with_f64 or same_bytes(F[:, rows].T, want[d][:, :20]), d
         assert np.all(X[:, ~inside] == S) and np.all(lab[~inside] == S)
         assert np.all(X[:, inside] != S) and np.all(lab[inside] != S)
         assert np.all(F[:, ~inside] == S) and (np.all(F[:, inside] != S) if with_f64 else np.all(F == S))
         outs.append(X)
-    assert np.array_equal(outs[0], outs[1])
+    assert np.array_equal(outs[0], outs[1]) and outs[0].tobytes() == outs[1].tobytes()
+
+
+def test_sentinels_behind_every_output(sgmm, g14):
+    """Rows outside row_off[d] .. +n_rows[d] stay untouched in X, F64 and label, for every
+    feature; without F64 the float32 matrix is the same."""
+    bars = fixture_bars(g14)
+    sentinel_launch(bars, [g14[f"d{k}_table"] for k in range(len(bars))])
+
+
+def test_sentinels_with_an_edge_day_among_the_fixture_days(sgmm, g14):
+    """The same launch with the rolling day between the fixture days: strides and gaps with
+    signed zeros, 1e300 and subnormal vwaps, with and without F64."""
+    bars = fixture_bars(g14)
+    want = [g14[f"d{k}_table"] for k in range(len(bars))]
+    bars.insert(2, fc.day("rolling"))
+    want.insert(2, fc.table("rolling")[0])
+    sentinel_launch(bars, want, whole=(2,))
 
 
 def all_events_bars(nb, seed=0):
@@ -217,6 +327,10 @@ def test_bars_per_day_guard(sgmm):
     ev = EventBarsGPU.from_bars([all_events_bars(4096), all_events_bars(7, seed=1)])
     ev.sgu1_table()
     assert ev.sgu1_n_rows.tolist() == [4096, 7]
+    # a full day of edge values: the last LDS slot of every per-bar array, 4096-step serial chains
+    ev, days = launch([fc.day("full")])
+    assert ev.sgu1_n_rows.tolist() == [4096]
+    assert_day_is_the_models(days[0], fc.table("full")[0], "full")
     ev = EventBarsGPU.from_bars([all_events_bars(4097)])
     with pytest.raises(_lib.SgmmError):
         ev.sgu1_table()
@@ -279,10 +393,24 @@ def test_hand_built_forests(sgmm):
 def test_depths(sgmm, depth):
     from sgmm_amd.gate_units import SGU1Forest
     rng = np.random.default_rng(100 + depth)
-    arrays = sm.random_forest(rng, 37, depth)  # 37: four groups of 8 trees and a tail of 5
+    arrays = sm.random_forest(rng, 37, depth)  # 37: two groups of 16 trees (SGMM_FOREST_ILP) and a tail of 5
     X = sm.random_rows(rng, 300)
     f = SGU1Forest.from_arrays(*arrays, 0.5)
     assert f.depth == depth
+    pred, leaf = sm.forest_predict(*arrays, np.float32(0.5), X)
+    assert np.array_equal(f.predict(X), pred) and np.array_equal(f.pred_leaf(X), leaf)
+
+
+def test_groups_and_tail_in_a_second_chunk(sgmm):
+    """701 trees at depth 4 over 65 rows: an LDS chunk of 666 trees, then 35 -- two full groups
+    of 16 and a tail of 3 inside the second chunk, and an odd count, so the uint2 tail copy runs
+    at a non-zero blob offset."""
+    from sgmm_amd.gate_units import SGU1Forest
+    rng = np.random.default_rng(701)
+    arrays = sm.random_forest(rng, 701, 4)
+    X = sm.random_rows(rng, 65)
+    f = SGU1Forest.from_arrays(*arrays, 0.5)
+    assert f.depth == 4 and f._blob.shape == (701, 46)
     pred, leaf = sm.forest_predict(*arrays, np.float32(0.5), X)
     assert np.array_equal(f.predict(X), pred) and np.array_equal(f.pred_leaf(X), leaf)
 

@@ -11,6 +11,7 @@ import numpy as np
 import pandas as pd
 import pytest
 
+import sgu1_feature_cases as fc
 import sgu1_model as sm
 from conftest import GOLDEN
 
@@ -181,6 +182,182 @@ def test_roll_mean_equals_pandas(w):
         fresh = np.array([v[max(i - w + 1, 0):i + 1].mean() for i in range(len(v))])
         fresh_differs += int((fresh != want).sum())
     assert w == 1 or fresh_differs > 0  # a fresh window mean is not what pandas computes
+
+
+# ---------------------------------------------------------------- the edge days (sgu1_feature_cases.py)
+
+EDGE_DAYS = fc.DAYS + tuple(str(k) for k, nb in enumerate(fc.TURNS) if nb >= 6)
+
+
+def shown(a):
+    """Per-bar values that reach the table: shift(1) drops the last bar's."""
+    return a[:-1]
+
+
+def halfway(v):
+    """+1 / -1 where the float64 v lies exactly between two neighbouring float32 values and the
+    cast moves it away from / towards zero, else 0."""
+    with np.errstate(over="ignore"):
+        f = np.asarray(v, np.float64).astype(np.float32)
+    out = np.zeros(len(f), np.int64)
+    for i, (a, b) in enumerate(zip(np.asarray(v, np.float64), f)):
+        if a == b or not np.isfinite(a):
+            continue
+        # the float32 neighbour on the other side of a, with 2^128 standing in for inf
+        with np.errstate(over="ignore"):
+            other = np.nextafter(b, np.float32(0 if abs(b) > abs(a) else np.copysign(np.inf, a)))
+        lo, hi = sorted((Fraction(2) ** 128 * int(np.sign(x)) if np.isinf(x) else Fraction(float(x)))
+                        for x in (b, other))
+        if Fraction(float(a)) - lo == hi - Fraction(float(a)):
+            out[i] = 1 if abs(float(b)) > abs(a) else -1
+    return out
+
+
+def test_edge_days_reach_their_edges():
+    """Conditions on the generators, from the model's intermediates: a day that misses one is
+    changed, never the count.  Measured: rolling (778 bars) 181 / 61 overriding all-equal rows
+    at windows 3 / 5, clamps 5 + 22 / 5 + 5, 185-206 bars per label arm, 78 vwaps of -0.0."""
+    _, st = fc.table("rolling")
+    assert len(st["vwap"]) < 1000
+    for w in (3, 5):
+        r = st["roll"][w]
+        assert shown(r["same"]).sum() >= 20, w
+        assert shown(r["clamp_nonneg"]).sum() >= 1 and shown(r["clamp_neg"]).sum() >= 1, w
+    for i, (_, sign, w) in enumerate(fc.CLAMPS):  # every stretch kept for a clamp hits it
+        hit = st["roll"][w]["clamp_nonneg" if sign > 0 else "clamp_neg"]
+        assert hit[fc.CLAMP_LEN * i + w:fc.CLAMP_LEN * (i + 1)].any(), i
+    assert np.bincount(st["branch"], minlength=5)[1:].min() >= 100
+    assert shown((st["vwap"] == 0) & np.signbit(st["vwap"])).sum() >= 4
+    v = st["vwap"]
+    assert (v > 9e299).any() and (v < -9e299).any() and np.isin([5e-324, -5e-324], v).all()
+    assert ((v > 0) & (v < 2e-300)).sum() >= 4
+
+    tab, st = fc.table("ties")
+    k = np.floor(st["x"] * 1e4)
+    tie = st["x"] * 1e4 == k + 0.5
+    assert (tie & (k % 2 == 0)).sum() >= 4 and (tie & (k % 2 == 1)).sum() >= 4
+    assert (tab[tie, 20] != np.floor(st["x"][tie] * 1e4 + 0.5) / 1e4).sum() >= 4
+    for arm in (1, 2, 3):  # a tie of each parity in every arm that can have one (none in arm 4: fc.tie_inputs)
+        assert (tie & (st["branch"] == arm) & (k % 2 == 0)).sum() >= 4, arm
+        assert (tie & (st["branch"] == arm) & (k % 2 == 1)).sum() >= 4, arm
+
+    tab, _ = fc.table("cast")
+    for cols in ((18,), (5,), (5, 18)):
+        F = tab[:, cols].ravel()
+        with np.errstate(over="ignore"):
+            X = F.astype(np.float32)
+        h = halfway(F)
+        classes = dict(inf=np.isinf(X) & np.isfinite(F), subnormal=(X != 0) & (np.abs(X) < 2.0 ** -126),
+                       zero=(X == 0) & (F != 0), half_away=h == 1, half_towards=h == -1)
+        for name, m in classes.items():
+            assert m.sum() >= 2, (cols, name)
+    with np.errstate(over="ignore"):
+        assert (np.isneginf(tab[:, 5].astype(np.float32)) & np.isfinite(tab[:, 5])).sum() >= 2
+
+    _, st = fc.table("hours")
+    assert st["hour"].tolist() == [t // 10 ** 7 for t in fc.HOURS]
+    assert {9, 10, 14, 0, 1}.issubset(st["hour"].tolist()) and st["hour"].max() > 2 ** 31 // 10 ** 7
+
+    for k, nb in enumerate(fc.TURNS):
+        if nb not in (1025, 2049):
+            continue
+        _, st = fc.table(str(k))
+        assert len(st["vwap"]) == nb
+        # the one bar of the last turn shows its label only: an arm no 1100- or 4096-bar day of
+        # all_events_bars reaches
+        assert st["branch"][-1] == (4 if nb == 1025 else 3)
+        if nb == 2049:  # a whole second turn: every arm, signed and -0.0 vwaps
+            assert set(st["branch"][1024:2048].tolist()) == {1, 2, 3, 4}
+            v = st["vwap"][1024:2048]
+            assert (v < 0).any() and ((v == 0) & np.signbit(v)).any()
+    _, st = fc.table("full")
+    assert len(st["vwap"]) == 4096 and set(st["branch"][3072:].tolist()) == {1, 2, 3, 4}
+
+
+@pytest.mark.parametrize("name", EDGE_DAYS)
+def test_edge_days_equal_pandas(name):
+    """pandas (2.3.3 when written) is the reference of the rolling means, the rounding and the
+    hour on every edge day: bytes, since array_equal hides the sign of zero."""
+    tab, st = fc.table(name)
+    ev = fc.turns()[int(name)] if name.isdigit() else fc.day(name)
+    assert len(tab) == len(st["vwap"]) >= 6
+    fill = lambda s: s.shift(1).ffill().bfill().to_numpy()
+    for j, w in enumerate((1, 3, 5)):
+        want = fill(pd.Series(st["vwap"]).rolling(w, min_periods=1).mean())
+        assert tab[:, 5 + j].tobytes() == want.tobytes(), (name, w, int((tab[:, 5 + j] != want).sum()))
+    label = np.round(st["x"], 4)
+    assert tab[:, 20].tobytes() == label.tobytes()
+    for L in range(1, 6):
+        assert tab[:, 10 + L].tobytes() == pd.Series(label).shift(L).ffill().bfill().to_numpy().tobytes(), L
+    first = np.asarray(ev["trade_time"])[::19][:len(tab)]
+    assert tab[:, 19].tobytes() == (first // 10 ** 7).astype(np.float64).tobytes()
+
+
+def roll_mean_mutant(v, w, mutation):
+    """sm.roll_mean with one rule changed: 'same', 'clamp_nonneg', 'clamp_neg' drop that
+    override, 'less_than_zero' counts x < 0 in place of signbit(x), 'one_compensation' shares
+    one Kahan compensation between adding and removing."""
+    v = np.asarray(v, np.float64)
+    out = np.empty(len(v))
+    isneg = (lambda x: x < 0) if mutation == "less_than_zero" else np.signbit
+    shared = mutation == "one_compensation"
+    s = c_add = c_rm = 0.0
+    nobs = neg = same = 0
+    prev = v[0]
+    for i in range(len(v)):
+        if w == 1 or i == 0:
+            s = c_add = c_rm = 0.0
+            nobs = neg = same = 0
+            prev = v[i]
+        elif i >= w:
+            x = v[i - w]
+            y = -x - (c_add if shared else c_rm)
+            t = s + y
+            c = t - s - y
+            c_add, c_rm = (c, c_rm) if shared else (c_add, c)
+            s = t
+            nobs -= 1
+            neg -= int(isneg(x))
+        x = v[i]
+        y = x - c_add
+        t = s + y
+        c_add = t - s - y
+        s = t
+        nobs += 1
+        neg += int(isneg(x))
+        same = same + 1 if x == prev else 1
+        prev = x
+        r = s / nobs
+        if same >= nobs and mutation != "same":
+            r = prev
+        elif same >= nobs:
+            pass
+        elif neg == 0 and r < 0 and mutation != "clamp_nonneg":
+            r = 0.0
+        elif neg == nobs and r > 0 and mutation != "clamp_neg":
+            r = 0.0
+        out[i] = r
+    return out
+
+
+def test_model_notices_the_mutations():
+    """Each rule of the rolling mean and of the rounding, changed in a copy, changes the table of
+    the day built for it; the unchanged copy does not."""
+    tab, st = fc.table("rolling")
+    p = np.maximum(np.arange(len(tab)) - 1, 0)
+    for j, w in ((6, 3), (7, 5)):
+        assert roll_mean_mutant(st["vwap"], w, None)[p].tobytes() == tab[:, j].tobytes()
+        for m in ("same", "clamp_nonneg", "clamp_neg", "less_than_zero", "one_compensation"):
+            got = roll_mean_mutant(st["vwap"], w, m)[p]
+            assert got.tobytes() != tab[:, j].tobytes(), (w, m)
+    # without the -0.0 bars x < 0 and signbit agree: those bars are what holds the rule
+    v = np.where(st["vwap"] == 0, 0.0, st["vwap"])
+    assert roll_mean_mutant(v, 3, "less_than_zero").tobytes() == sm.roll_mean(v, 3).tobytes()
+    tab, st = fc.table("ties")
+    y = st["x"] * 1e4
+    half_away = np.copysign(np.floor(np.abs(y) + 0.5), y) / 1e4
+    assert (half_away != tab[:, 20]).sum() >= 4
+    assert ((np.floor(y + 0.5) / 1e4) != tab[:, 20]).sum() >= 4
 
 
 def test_slope_closed_form_against_exact_fractions(g14):
